@@ -11,12 +11,17 @@ A "step" is one forward pass (`no_grad`) of the workload's module over one synth
 no data-path collective in the forward (weak scaling).  `value` = whole-job timesteps/s =
 N * T / t_step, t_step = max over ranks of the mean step time.
 
+A plain run sets up, warms up, times `--steps` steps, writes the last step's results if
+`--dump-outputs DIR` is given, and prints the line.  `--full` adds the legs that run steps of their own
+after the timed region (N=1): ms_per_step_median / ms_per_step_blocks, other_fp32_math, prepared (and
+with it the recurrent kernel alone as the roofline's kernel_ms), cpu_baseline / gpu_over_cpu.
+
 Extra objects on the JSON line:
   roofline      compute roofline of the dominant kernel (ttrnn_rnn_forward): algorithmic FLOP per
                 launch (691 712 FLOP per sample-timestep for cfg2) / the kernel's
                 mean duration measured with events on its launch stream; peak = 157.3 TFLOP/s fp32.
-  cpu_baseline  the oracle's op-for-op torch-CPU restatement of the reference path ("port") timed
-                on this host's cores on the same workload (rank 0, N=1 only).
+  cpu_baseline  (--full) the oracle's op-for-op torch-CPU restatement of the reference path ("port")
+                timed on this host's cores on the same workload (rank 0, N=1 only).
 """
 import argparse
 import contextlib
@@ -193,6 +198,36 @@ def build_model(w, device):
     if w["dtype"] == "bf16":
         m = m.to(torch.bfloat16)
     return m.eval()
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000      # --dump-outputs writes at most 64 MB in all; headers and rounding stay inside the rest
+
+
+def dump_outputs(out_dir, last, kind):
+    """--dump-outputs: what the last timed step returned, as <out_dir>/<name>.npy in float32.  Forward: (outputs, h_n) of the
+    GRU, (outputs, (h_n, c_n)) of the LSTM; train: the loss.  The arrays share DUMP_BUDGET_BYTES, smallest first; one that does
+    not fit its share is stored as a sample of its flattened elements at indices drawn once from a generator seeded with a
+    constant and the array's size, so two builds sample the same elements."""
+    import numpy as np
+    if kind == "train":
+        named = [("loss", last)]
+    elif kind == "ttlstm":
+        named = [("outputs", last[0]), ("h_n", last[1][0]), ("c_n", last[1][1])]
+    else:
+        named = [("outputs", last[0]), ("h_n", last[1])]
+    os.makedirs(out_dir, exist_ok=True)
+    named.sort(key=lambda nt: nt[1].numel())
+    left = DUMP_BUDGET_BYTES
+    for i, (name, t) in enumerate(named):
+        a = t.detach().float().cpu().contiguous()
+        share = left // (len(named) - i) // 4              # elements this array may take
+        if a.numel() > share:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(20240229 + a.numel())
+            idx = torch.randint(a.numel(), (share,), generator=g)
+            a = a.reshape(-1)[idx]
+        left -= a.numel() * 4
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
 
 
 def physical_cores():
@@ -407,7 +442,19 @@ def main():
                     help="train mode / grid --mode train: record the step once into a hipGraph (ttrnn_hip.CapturedTrainStep) and "
                          "time REPLAYS — one host call per step instead of 30 ... 110 launches through ctypes and autograd.  "
                          "Opt-in; the line says so in config.mode.  Single process only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the dispersion blocks "
+                         "(ms_per_step_median / ms_per_step_blocks), the same steps in the other fp32 math mode (other_fp32_math) and "
+                         "on prepared modules (prepared, the recurrent kernel alone for the roofline), and the CPU baseline "
+                         "(cpu_baseline, gpu_over_cpu; --no-cpu-baseline leaves that leg out).  Off by default: a plain run sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float32; forward: "
+                         "outputs, h_n and for the LSTM c_n; train: loss), at most 64 MB in all: a larger array is stored as a fixed, "
+                         "seeded sample of its elements.  Rank 0 writes")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.graph and args.mode != "train":
         raise SystemExit("--graph captures a TRAINING step: use it with --mode train")
     if args.graph and args.gpus > 1:
@@ -571,10 +618,14 @@ def main():
     elapsed = time.perf_counter() - t0
     timer.enabled = False
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, "train" if args.mode == "train" else w["kind"])
+
     # Dispersion of the headline WITHOUT events in the queue: the same step again in 5 blocks of `steps`,
     # a device synchronisation around each block — outside the timed region above; min / median / max of the block means.
+    # (--full only, like every other leg below that runs steps of its own.)
     blocks_ms = None
-    if world == 1 and args.steps >= 4:
+    if args.full and world == 1 and args.steps >= 4:
         bm = []
         for _ in range(5):
             torch.cuda.synchronize()
@@ -628,7 +679,7 @@ def main():
     # in the OTHER mode, so that both figures come from one process on one device (outside the timed region above)
     math_mode = ttrnn_hip.get_fp32_math() if w["dtype"] == "f32" else None
     other = None
-    if math_mode is not None and args.mode == "forward" and world == 1:
+    if args.full and math_mode is not None and args.mode == "forward" and world == 1:
         alt = "exact" if math_mode == "split" else "split"
         with ttrnn_hip.fp32_math(alt):
             for _ in range(args.warmup):
@@ -644,7 +695,7 @@ def main():
     # the same steps on prepared modules (weight-only work kept across forwards) — beside the headline, never the headline
     prepared_extra = None
     rec_only_ms = None
-    if args.mode == "forward" and not prepared and world == 1:
+    if args.full and args.mode == "forward" and not prepared and world == 1:
         model.prepare_for_inference()
         for _ in range(args.warmup):
             step()
@@ -840,7 +891,7 @@ def main():
             line["other_fp32_math"] = other
         if prepared_extra is not None:
             line["prepared"] = prepared_extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(w, rnn_module.state_dict(), x)
             line["gpu_over_cpu"] = line["value"] / line["cpu_baseline"]["value"]
         payload = json.dumps(line)

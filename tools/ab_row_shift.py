@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 w = sys.argv[1] if len(sys.argv) > 1 else "cfg5"
 steps = sys.argv[2] if len(sys.argv) > 2 else "15"
 code = ("import sys; sys.path.insert(0, %r); sys.argv = ['bench.py', '--workload', %r, '--mode', 'train', '--steps', %r, "
-        "'--warmup', '3', '--no-cpu-baseline']; import bench; import ttrnn_hip.functional as F; "
+        "'--warmup', '3', '--full', '--no-cpu-baseline']; import bench; import ttrnn_hip.functional as F; "
         "F.USE_ROW_SHIFT = bool(%d); F.USE_BWD_STATS = bool(%d); bench.main()")
 for rep in range(2):
     for shift, stats in ((1, 1), (0, 1), (0, 0)):

@@ -8,17 +8,17 @@ QUICK=${2:-}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for w in cfg2 cfg1 cfg3 cfg4 cfg5; do
-  timeout 600 python bench.py --workload $w --steps 20 --warmup 5 > $OUT/bench_$w.json 2> $OUT/bench_$w.err
+  timeout 600 python bench.py --full --workload $w --steps 20 --warmup 5 > $OUT/bench_$w.json 2> $OUT/bench_$w.err
 done
 # the reference's own GRU dtype (fp32) at cfg3's and cfg2's sizes (round 5: k_gru_fwd_f10vh)
 for w in cfg3_fp32 gru64; do
-  timeout 600 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_$w.json 2> $OUT/bench_$w.err
-  timeout 600 python bench.py --workload $w --mode train --steps 8 --warmup 3 --no-cpu-baseline > $OUT/bench_train_$w.json 2> $OUT/bench_train_$w.err
+  timeout 600 python bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_$w.json 2> $OUT/bench_$w.err
+  timeout 600 python bench.py --full --workload $w --mode train --steps 8 --warmup 3 --no-cpu-baseline > $OUT/bench_train_$w.json 2> $OUT/bench_train_$w.err
 done
 for w in cfg2 cfg3 cfg4 cfg5; do
-  timeout 600 python bench.py --workload $w --mode train --steps 8 --warmup 3 --no-cpu-baseline > $OUT/bench_train_$w.json 2> $OUT/bench_train_$w.err
+  timeout 600 python bench.py --full --workload $w --mode train --steps 8 --warmup 3 --no-cpu-baseline > $OUT/bench_train_$w.json 2> $OUT/bench_train_$w.err
 done
-TTRNN_BENCH_FORCE_DIST=1 timeout 600 python bench.py --workload cfg2 --mode train --steps 8 --warmup 3 --no-cpu-baseline > $OUT/bench_train_cfg2_rccl1.json 2> $OUT/bench_train_cfg2_rccl1.err
+TTRNN_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --workload cfg2 --mode train --steps 8 --warmup 3 --no-cpu-baseline > $OUT/bench_train_cfg2_rccl1.json 2> $OUT/bench_train_cfg2_rccl1.err
 [ -x tools/bin/gemm3_bench ] && tools/bin/gemm3_bench 131072 1024 4096 4 > $OUT/gemm3_cfg5.log 2>&1
 if [ -z "$QUICK" ]; then
   timeout 900 python bench.py --workload grid > $OUT/bench_grid.json 2> $OUT/bench_grid.err
