@@ -303,6 +303,10 @@ int ttrnn_rnn_forward_route(const ttrnn_rnn_desc* desc);   /* TTRNN_ROUTE_* or a
  * the naive per-gate sets of tt_linearset.py:5-38 at benchmarking.py's defaults).  Pure host logic; a negative ttrnn_status on a
  * bad descriptor. */
 int ttrnn_rnn_forward_samples_per_workgroup(const ttrnn_rnn_desc* desc);
+/* 1 when the recurrent forward kernel of this descriptor contracts cores 0·1 of the hidden matrix first (k_lstm_fwd_f10t: TT-LSTM
+ * H = 256, d = 3, r = 8, split math mode, no more samples than CUs; option dev2 bit 2048 keeps k_lstm_fwd_f10q), else 0.  Pure
+ * host logic; a negative ttrnn_status on a bad descriptor. */
+int ttrnn_rnn_forward_cores01_first(const ttrnn_rnn_desc* desc);
 
 /* Reverse-time part of BPTT (reference: torch autograd through lstm.py:123-133 / gru.py:124-134).
  *   d_out[B][T][H], d_hT/d_cT[B][H] (any may be NULL = zeros)

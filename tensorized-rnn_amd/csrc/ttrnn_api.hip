@@ -864,6 +864,15 @@ int ttrnn_rnn_forward_samples_per_workgroup(const ttrnn_rnn_desc* desc) {
   return (route == TTRNN_ROUTE_RUNTIME_MFMA && g2_rnn_fwd_paired(rs)) ? 2 : 1;
 }
 
+int ttrnn_rnn_forward_cores01_first(const ttrnn_rnn_desc* desc) {
+  const int route = ttrnn_rnn_forward_route(desc);
+  if (route < 0) return route;
+  RnnShape rs;
+  if (rnn_shape_init(&rs, desc) != TTRNN_OK) return TTRNN_ERR_BAD_DESC;
+  if (route != TTRNN_ROUTE_FUSED_CORE || rs.B < 1 || rs.T < 1 || w2_rnn_fwd_available(rs, desc->dtype) || fwd_prefers_g2(rs, desc->dtype)) return 0;
+  return desc->dtype == TTRNN_F32 && fp32_math() == TTRNN_MATH_SPLIT && plan_fast_fwd(rs, desc->dtype).use && f10_fwd_takes_f10t(rs) ? 1 : 0;
+}
+
 int ttrnn_rnn_backward_route(const ttrnn_rnn_desc* desc, int want_state) {
   RnnShape rs;
   if (rnn_shape_init(&rs, desc) != TTRNN_OK) return TTRNN_ERR_BAD_DESC;

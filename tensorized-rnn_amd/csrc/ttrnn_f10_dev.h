@@ -394,4 +394,101 @@ __global__ void __launch_bounds__(256) k_f10h_scale(const float* __restrict__ pa
   }
 }
 
+// ---- cores 0·1 FIRST (round 7: k_lstm_fwd_f10t, ttrnn_fast_f10t.hip) -----------------------------------------------------------
+// The other contraction order: D[(m, r2)][j2] = sum_{k = (j0, j1)} W10[m][k][r2] h[k][j2] (K = 32), then out[m][i2] = sum_{(r2, j2)}
+// D[m][(r2, j2)] G2[(r2, j2)][i2] (K = 64).  Same diagonal exponents eu / ev as above (they depend on core 2 only: read from the
+// header); the row exponent of the fused core comes from the rows' L1 norms over k, because |D'| <= L1_k(W10' row) max |h'| is
+// what has to fit fp16:
+//   h' = 2^4 h                                         (|h_t| < 1; smaller than the old order's 2^6: the room goes to the rows)
+//   W10t'[m][k][r2] = W10 2^(ept[m] - ev[r2]) x gate factor,   ept[m] = 10 - expo(max_r2 2^-ev[r2] sum_k |W10[m][k][r2]|)
+//   |D'| < 2^10 x 2.886 x 2^4 = 2^15.53 < 65 504:  inside fp16 (second pieces normal down to |D'| = 2^-3)
+//   G2t'[r2][j2][i2] = G2 2^(12 + eu[i2] + ev[r2])     every entry < 2^12
+//   accumulators     acc[m][i2] = 2^(ept[m] + eu[i2] + 16) x gate factor x pre-activation
+// (tools/f10t_scale_sim.py rehearses these on the operand-range / outlier weight sets of the tests.)
+// The workspace of the shape has no room for a second set of fragments next to the old-order ones (its size is part of the host
+// API's contract: 96 KB, 65 KB used), so the kernel builds its own in its prologue, from the packed cores: 128 entries of eight
+// multiply-adds per lane, once per launch (the same fmaf chain and the same pinned split2h_scaled as k_f10h_prep).
+static constexpr int F10T_ROW_EXP = 10;        // row L1 norms of the scaled fused core < 2^10
+static constexpr int F10T_ACC_EXP = 16;        // 4 (h) + 12 (core 2)
+static constexpr float F10T_HSC = 16.0f;       // 2^4: the scale of h
+// Stage 1's B operand (two fp16 pieces) of wave `wave`: lane (c, q) holds row m = 16 (c & 3) + 4 wave + (c >> 2), k = 8 q + e
+// (j0 = q, j1 = e) of every rank slice r2.  Returns ept[m] of the lane's row (the same in the four lanes q of a column c).
+template <class S>
+__device__ __forceinline__ int f10t_build_w10(xh8 (&w10)[8][2], const float* packed, const float* __restrict__ hdr, int wave, int lane) {
+  using F = F10<S>;
+  static_assert(F::R2 == 8 && F::J0 == 4 && F::J1 == 8 && F::R1 == 8 && F::M == 64 && F::MPG == 16, "H = 256, r = 8");
+  const int c = lane & 15, q = lane >> 4;
+  const int* ev = reinterpret_cast<const int*>(hdr) + F10H_EV;
+  const int g = c & 3, m = F::MPG * g + 4 * wave + (c >> 2);
+  const int i0 = m / F::I1, i1 = m % F::I1;
+  const float* W0 = packed + woff_of<S>(0);               // [J0*R1][I0]
+  const float* W1 = packed + woff_of<S>(1);               // [J1*R2][I1*R1]
+  float w0[F::R1];
+#pragma unroll
+  for (int r1 = 0; r1 < F::R1; ++r1) w0[r1] = W0[(q * F::R1 + r1) * F::I0 + i0];
+  auto entry = [&](int e, int r2) {
+    const float* w1p = W1 + (e * F::R2 + r2) * (F::I1 * F::R1) + i1 * F::R1;
+    float v = 0.f;
+#pragma unroll
+    for (int r1 = 0; r1 < F::R1; ++r1) v = fmaf(w0[r1], w1p[r1], v);
+    return v;
+  };
+  float best = 0.f;
+#pragma unroll      // (kept as a loop this pass costs MORE registers: 238 VGPRs against 196 — the prologue, not the time loop, sets the count)
+  for (int r2 = 0; r2 < F::R2; ++r2) {
+    float l1 = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) l1 += fabsf(entry(e, r2));
+    l1 += __shfl_xor(l1, 16);                             // the four k-groups of the row: the same sum in all four lanes
+    l1 += __shfl_xor(l1, 32);
+    best = fmaxf(best, l1 * ldexpf(1.f, -ev[r2]));
+  }
+  const int ept = F10T_ROW_EXP - f10h_expo(best);
+  const float gf = g == 2 ? 2.8853900817779268f : -1.4426950408889634f;
+#pragma unroll
+  for (int r2 = 0; r2 < F::R2; ++r2) {
+    const float sc = gf * ldexpf(1.f, ept - ev[r2]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      _Float16 p0, p1;
+      split2h_scaled(entry(e, r2), sc, p0, p1);           // (pinned rounding: ttrnn_split.h)
+      w10[r2][0][e] = p0; w10[r2][1][e] = p1;
+    }
+  }
+  return ept;
+}
+// per lane: 2^(ept[m_j] + eu[c] + 16) for the lane's four accumulator rows m_j = MPG j + 4 wave + q (stage-1 column 4 q + j), and
+// the inverse; ept_mine: f10t_build_w10's answer for this lane
+__device__ __forceinline__ F10hScales f10t_scales(const float* __restrict__ hdr, int ept_mine, int lane) {
+  const int* e = reinterpret_cast<const int*>(hdr);
+  const int c = lane & 15, q = lane >> 4;
+  const int eu = e[F10H_EU + c];
+  F10hScales r;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int s = __shfl(ept_mine, 4 * q + j) + eu + F10T_ACC_EXP;
+    r.pre[j] = ldexpf(1.f, s);
+    r.un[j] = ldexpf(1.f, -s);
+  }
+  return r;
+}
+// stage 2's B operand from core 2, built by the recurrent kernel itself: lane (c, q) holds column i2 = c, k = 8 q + j of k-block kb
+// <-> rank index r2 = 2 kb + (j >> 2) + 4 (q >> 1), j2 = 4 (q & 1) + (j & 3)  (the order the folded stage-1 tiles arrive in)
+template <class S>
+__device__ __forceinline__ void f10t_load_g2(xh8 (&g2)[2][2], const float* packed, int lane, const float* __restrict__ hdr) {
+  using F = F10<S>;
+  const int c = lane & 15, q = lane >> 4;
+  const float* W2 = packed + woff_of<S>(2);               // [J2][M2], m2 = i2 R2 + r2
+  const int* e = reinterpret_cast<const int*>(hdr);
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int r2 = 2 * kb + (j >> 2) + 4 * (q >> 1), j2 = 4 * (q & 1) + (j & 3);
+      _Float16 p0, p1;
+      split2h(W2[j2 * F::M2 + c * F::R2 + r2] * ldexpf(1.f, 12 + e[F10H_EU + c] + e[F10H_EV + r2]), p0, p1);
+      g2[kb][0][j] = p0; g2[kb][1][j] = p1;
+    }
+}
+
 }  // namespace ttrnn

@@ -846,6 +846,9 @@ static int launch_f10(const RnnShape& rs, GinSrc gin, const void* h0, const void
     // one barrier per step, S2 inside the gate waves (ttrnn_fast_f10s.hip, round 5): measured slower, dev bit 512 selects it (A/B)
     if (KS == 1 && f10s_available(rs, h0 != nullptr))
       return launch_rnn_fwd_f10_s(rs, gin, h0, c0, packed_hid, ws, bh, out, hT, cT, reserve, stream);
+    // cores 0·1 first, stage hand-off in registers (ttrnn_fast_f10t.hip, round 7): r = 8 while every sample has its own CU
+    if (KS == 1 && f10t_available(rs))
+      return launch_rnn_fwd_f10_t(rs, gin, h0, c0, packed_hid, ws, bh, out, hT, cT, reserve, stream);
     if (KS == 1 || 2 * rs.B > cus)
       return launch_rnn_fwd_f10_q(rs, gin, h0, c0, packed_hid, ws, bh, out, hT, cT, reserve, stream);
   }
@@ -865,6 +868,13 @@ size_t f10_workspace_bytes(const RnnShape& rs, int dtype) {
   if (shape_matches<ShpH256R8L>(rs.hid_s)) return f10_wfrag_bytes<ShpH256R8L>();
   if (shape_matches<ShpH256R16L>(rs.hid_s)) return f10_wfrag_bytes<ShpH256R16L>();
   return f2_workspace_bytes(rs, dtype);      // two-core hidden matrices (ttrnn_fast_f2.hip)
+}
+
+// does launch_f10 hand this call to k_lstm_fwd_f10t (ttrnn_rnn_forward_cores01_first: the tests assert the route)?
+bool f10_fwd_takes_f10t(const RnnShape& rs) {
+  if (rs.cell != TTRNN_LSTM || !shape_matches<ShpH256R8L>(rs.hid_s) || opt(OPT_F10_NB1)) return false;
+  if (rs.B > device_cu_count() && opt(OPT_F10_NB2)) return false;
+  return !f10s_available(rs, false) && f10t_available(rs);
 }
 
 bool f10_rnn_fwd_available(const RnnShape& rs, int dtype) {

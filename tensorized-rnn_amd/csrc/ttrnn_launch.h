@@ -188,6 +188,13 @@ bool f10gh_own_plan(const RnnShape& rs);      // the shape has the file's own in
 int launch_rnn_fwd_f10_nb2(const RnnShape& rs, GinSrc gin, const void* h0, const void* c0, const float* packed_hid,
                            const void* wfrag, const float* bias_hid, void* out, void* hT, void* cT, float* reserve,
                            hipStream_t stream);
+// cores 0·1 first (ttrnn_fast_f10t.hip): H = 256, r = 8, one sample per CU; ws as launch_rnn_fwd_f10_q (only the header's eu / ev
+// are read: the kernel builds its own fragments from packed_hid)
+bool f10t_available(const RnnShape& rs);
+bool f10_fwd_takes_f10t(const RnnShape& rs);      // launch_rnn_fwd_f10's routing, for ttrnn_rnn_forward_cores01_first
+int launch_rnn_fwd_f10_t(const RnnShape& rs, GinSrc gin, const void* h0, const void* c0, const float* packed_hid,
+                         const void* ws, const float* bias_hid, void* out, void* hT, void* cT, float* reserve,
+                         hipStream_t stream);
 int launch_rnn_fwd_f10_q(const RnnShape& rs, GinSrc gin, const void* h0, const void* c0, const float* packed_hid,
                            const void* wfrag, const float* bias_hid, void* out, void* hT, void* cT, float* reserve,
                            hipStream_t stream);

@@ -666,6 +666,15 @@ def rnn_samples_per_workgroup(spec, batch, seq_len, dtype=torch.float32):
     return n
 
 
+def rnn_cores01_first(spec, batch, seq_len, dtype=torch.float32):
+    """True when the recurrent forward kernel for this layer at this size contracts cores 0·1 first (k_lstm_fwd_f10t)."""
+    desc = spec.desc(batch, seq_len, _DT[dtype])
+    n = _lib.load().ttrnn_rnn_forward_cores01_first(ctypes.byref(desc))
+    if n < 0:
+        check(n, "ttrnn_rnn_forward_cores01_first")
+    return bool(n)
+
+
 def rnn_backward_route(spec, batch, seq_len, dtype=torch.float32, want_state=False):
     """Name of the kernel family of the reverse-time kernel (BPTT) for this layer at this size."""
     desc = spec.desc(batch, seq_len, _DT[dtype])
