@@ -59,9 +59,14 @@ class SpeakerEncoder(nn.Module):
         self.similarity_weight = nn.Parameter(torch.tensor([10.]))
         self.similarity_bias = nn.Parameter(torch.tensor([-5.]))
 
-    def forward(self, utterances):
+    def forward(self, utterances, lengths=None):
+        """lengths: optional frames per utterance of a batch padded to a common length (LSTM.forward's `lengths`): the embedding
+        of utterance b is that of utterances[b, :lengths[b]] run alone (examples/embed_utterances.py)."""
         # only the last layer's final hidden state is consumed (speaker_encoder.py:80-86): inference skips its [B, T, H] outputs
-        res = self.rnn(utterances) if torch.is_grad_enabled() else self.rnn(utterances, need_outputs=False)
+        if lengths is not None:
+            res = self.rnn(utterances, need_outputs=torch.is_grad_enabled(), lengths=lengths)
+        else:
+            res = self.rnn(utterances) if torch.is_grad_enabled() else self.rnn(utterances, need_outputs=False)
         last_hidden = res[1] if self.use_gru else res[1][0]
         return self.linear.forward_head(last_hidden, "relu_l2norm")              # TTLinear + ReLU + L2 norm: one library call
 

@@ -308,6 +308,46 @@ int ttrnn_rnn_forward_samples_per_workgroup(const ttrnn_rnn_desc* desc);
  * host logic; a negative ttrnn_status on a bad descriptor. */
 int ttrnn_rnn_forward_cores01_first(const ttrnn_rnn_desc* desc);
 
+/* ---- per-sample sequence lengths (additive to ABI 7: test for TTRNN_HAS_VARLEN) ------------------------------------------------
+ * The reference's caller embeds whole utterances of arbitrary length one call at a time
+ * (experiments/speaker_verification/encoder/inference.py:110-154, "TODO: handle multiple wavs to benefit from batching on GPU");
+ * these entry points run a batch of sequences of DIFFERENT lengths, padded to T, in one call.
+ *   lengths  int32[B], DEVICE memory; lengths[b] in [1, T].  They cannot be validated without a synchronisation: the kernels
+ *            clamp them to [0, T] for memory safety, and an out-of-range value is a caller error confined to that sample.
+ * Semantics (one definition):
+ *   - sample b behaves exactly like that sample run alone on x[b][0 .. len_b);
+ *   - out[b][t][:] = 0 for t >= len_b (zero padding, as torch's pad_packed_sequence);
+ *   - hT[b] / cT[b] are the state after step len_b - 1;
+ *   - rows x[b][t] with t >= len_b never influence a forward result.  They MUST BE FINITE all the same: the weight-gradient
+ *     kernels multiply them by exact zeros.
+ * Frozen records.  With reserve != NULL the forward writes, for every t >= len_b, a record in the reserve layout above:
+ *   LSTM  (i, g, f, o) = (0, 0, 1, 0) and c_t = c_{len_b - 1};        GRU  (r, z, n, hidden_part_n) = (0, 1, 0, 0).
+ * Every reverse-time kernel's gate gradients are products of the stored gate values: on a frozen record they are exact zeros,
+ * and dc (LSTM) / dh (GRU) pass through unchanged — no reverse kernel knows about lengths.  What an LSTM's frozen steps drop is
+ * dh (W^T times zero gate gradients), so the gradient of hT has to enter at the sample's own last row; d_cT needs nothing (it
+ * flows through f = 1).  A training step therefore is
+ *   ttrnn_rnn_forward_varlen(..., reserve, ...)
+ *   ttrnn_rnn_varlen_seed_dout(desc, lengths, d_out, d_hT, d_out_seeded, stream)
+ *       d_out_seeded[b][t] = (t < len_b ? d_out[b][t] : 0) + (t == len_b - 1 ? d_hT[b] : 0)     (storage dtype, [B][T][H];
+ *       d_out and d_hT may each be NULL = zeros; d_out_seeded may not alias d_out)
+ *   ttrnn_rnn_backward_ex(..., d_out = d_out_seeded, d_hT = NULL, d_cT as given, ...)            (GRU too: one rule)
+ *   ttrnn_rnn_wgrad / ttrnn_ttlinear_backward_hinted                                              unchanged.
+ * Kernels.  ttrnn_rnn_forward_varlen_route reports the family that takes the call under the current options (dev2, force_generic,
+ * fp32_math as ttrnn_rnn_forward_route): TTRNN_ROUTE_FUSED_CORE for the encoder-shape kernels (H = 768, 40 inputs), otherwise
+ * TTRNN_ROUTE_RUNTIME_MFMA (always one sample per workgroup) or TTRNN_ROUTE_VALU.  The other shape-specialised forward kernels
+ * do not take lengths; their shapes run the runtime tier.  Each workgroup's time loop ends at its own sample's length.
+ * Conventions as everywhere: no allocation, no synchronisation, capture-safe (lengths are read on the device at replay time);
+ * out == NULL is accepted for an inference call; workspace of ttrnn_rnn_varlen_workspace(desc) bytes. */
+#define TTRNN_HAS_VARLEN 1
+int ttrnn_rnn_forward_varlen_route(const ttrnn_rnn_desc* desc);   /* TTRNN_ROUTE_* or a negative ttrnn_status */
+size_t ttrnn_rnn_varlen_workspace(const ttrnn_rnn_desc* desc);
+int ttrnn_rnn_forward_varlen(const ttrnn_rnn_desc* desc, const int32_t* lengths, const void* x, const void* h0, const void* c0,
+                             const float* packed_in, const void* bias_in, const float* packed_hid, const void* bias_hid,
+                             void* out, void* hT, void* cT, float* reserve, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int ttrnn_rnn_varlen_seed_dout(const ttrnn_rnn_desc* desc, const int32_t* lengths, const void* d_out, const void* d_hT,
+                               void* d_out_seeded, void* stream);
+
 /* Reverse-time part of BPTT (reference: torch autograd through lstm.py:123-133 / gru.py:124-134).
  *   d_out[B][T][H], d_hT/d_cT[B][H] (any may be NULL = zeros)
  *   -> d_gates_in[B][T][G*H], d_gates_hid[B][T][G*H] (fp32: gradients w.r.t. the outputs of the

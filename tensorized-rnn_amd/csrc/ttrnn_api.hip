@@ -856,6 +856,73 @@ int ttrnn_rnn_forward_route(const ttrnn_rnn_desc* desc) {
   return TTRNN_ROUTE_VALU;
 }
 
+// ---- per-sample sequence lengths (include/ttrnn.h) -----------------------------------------------------------------------------
+// Three forward kernels take lengths: the encoder-shape kernels (ttrnn_fast_w2.hip), the runtime-shape kernel on its unpaired plan
+// (k_g2_fwd) and the any-shape kernel (rnn_fwd_body).  The other shape-specialised forward families do not: their shapes run the
+// runtime tier here.  The reserve they leave is everybody's format, so the reverse-time route is chosen as for any other call.
+static int varlen_route(const RnnShape& rs, int dtype) {
+  if (force_generic()) return TTRNN_ROUTE_VALU;
+  if (rs.T > 0 && w2_rnn_fwd_available(rs, dtype)) return TTRNN_ROUTE_FUSED_CORE;
+  if (g2_rnn_varlen_available(rs, dtype)) return TTRNN_ROUTE_RUNTIME_MFMA;
+  return TTRNN_ROUTE_VALU;
+}
+
+int ttrnn_rnn_forward_varlen_route(const ttrnn_rnn_desc* desc) {
+  RnnShape rs;
+  if (rnn_shape_init(&rs, desc) != TTRNN_OK) return TTRNN_ERR_BAD_DESC;
+  return varlen_route(rs, desc->dtype);
+}
+
+size_t ttrnn_rnn_varlen_workspace(const ttrnn_rnn_desc* desc) {
+  RnnShape rs;
+  if (rnn_shape_init(&rs, desc) != TTRNN_OK) return 0;
+  switch (varlen_route(rs, desc->dtype)) {
+    case TTRNN_ROUTE_FUSED_CORE: return w2_rnn_fwd_workspace_bytes();
+    case TTRNN_ROUTE_RUNTIME_MFMA: return g2_rnn_fwd_varlen_workspace(rs);
+  }
+  return plan_rnn_generic(rs, false).ws_bytes;
+}
+
+int ttrnn_rnn_forward_varlen(const ttrnn_rnn_desc* desc, const int32_t* lengths, const void* x, const void* h0, const void* c0,
+                             const float* packed_in, const void* bias_in, const float* packed_hid, const void* bias_hid,
+                             void* out, void* hT, void* cT, float* reserve, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  RnnShape rs;
+  int st = rnn_shape_init(&rs, desc);
+  if (st != TTRNN_OK) return st;
+  if (rs.B == 0) return TTRNN_OK;
+  if (!lengths || !packed_in || !packed_hid) return TTRNN_ERR_NULL;
+  if (rs.T > 0 && (!x || (!out && !out_optional(rs, desc->dtype, reserve != nullptr)))) return TTRNN_ERR_NULL;
+  if (rs.has_bias_in && !bias_in) return TTRNN_ERR_NULL;
+  if (rs.has_bias_hid && !bias_hid) return TTRNN_ERR_NULL;
+  const int* lens = reinterpret_cast<const int*>(lengths);
+  switch (varlen_route(rs, desc->dtype)) {
+    case TTRNN_ROUTE_FUSED_CORE:
+      if (!workspace || workspace_bytes < w2_rnn_fwd_workspace_bytes()) return TTRNN_ERR_WORKSPACE;
+      return launch_rnn_fwd_w2(rs, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, workspace,
+                               (hipStream_t)stream, TTRNN_PHASE_ALL, lens);
+    case TTRNN_ROUTE_RUNTIME_MFMA:
+      if (!workspace || workspace_bytes < g2_rnn_fwd_varlen_workspace(rs)) return TTRNN_ERR_WORKSPACE;
+      return launch_rnn_fwd_g2(rs, desc->dtype, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve,
+                               workspace, (hipStream_t)stream, lens);
+  }
+  const RnnPlan p = plan_rnn_generic(rs, false);
+  if (p.ws_bytes > 0 && (!workspace || workspace_bytes < p.ws_bytes)) return TTRNN_ERR_WORKSPACE;
+  return launch_rnn_fwd_generic(rs, p, desc->dtype, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT,
+                                reserve, workspace, (hipStream_t)stream, lens);
+}
+
+int ttrnn_rnn_varlen_seed_dout(const ttrnn_rnn_desc* desc, const int32_t* lengths, const void* d_out, const void* d_hT,
+                               void* d_out_seeded, void* stream) {
+  RnnShape rs;
+  int st = rnn_shape_init(&rs, desc);
+  if (st != TTRNN_OK) return st;
+  if (rs.B == 0 || rs.T == 0) return TTRNN_OK;
+  if (!lengths || !d_out_seeded) return TTRNN_ERR_NULL;
+  return launch_varlen_seed_dout(desc->dtype, rs.B, rs.T, rs.H, reinterpret_cast<const int*>(lengths), d_out, d_hT, d_out_seeded,
+                                 (hipStream_t)stream);
+}
+
 int ttrnn_rnn_forward_samples_per_workgroup(const ttrnn_rnn_desc* desc) {
   const int route = ttrnn_rnn_forward_route(desc);
   if (route < 0) return route;

@@ -136,6 +136,9 @@ inline int rnn_shape_init(RnnShape* r, const ttrnn_rnn_desc* d) {
 // generic stage bodies (one thread's share)
 // ------------------------------------------------------------------------------------------------
 template <typename T> TT_HD T tmin(T a, T b) { return a < b ? a : b; }
+template <typename T> TT_HD T tmax(T a, T b) { return a > b ? a : b; }
+// a caller's per-sample length, made safe for memory (lengths cannot be validated without a synchronisation: include/ttrnn.h)
+TT_HD int varlen_clamp(int len, int T) { return len < 0 ? 0 : (len > T ? T : len); }
 
 // Training reserve (include/ttrnn.h).  LSTM: the activated gates [B*T][H][4] (i,g,f,o: one 16-byte record per hidden unit)
 // followed by the cell states [B*T][H] — five floats per unit and step, not a padded record of eight.  GRU: [B*T][H][4]
@@ -542,10 +545,29 @@ TT_HD void rnn_fwd_body(Ex& ex, const RnnShape& rs, int b0, int nb,
                         const T* x, const T* h0, const T* c0,
                         const float* Win, const T* bin, const float* Whid, const T* bhid,
                         T* out, T* hT, T* cT, float* reserve,
-                        float* bufA, float* bufB, float* hbuf, float* cbuf, float* gin) {
+                        float* bufA, float* bufB, float* hbuf, float* cbuf, float* gin, const int* lens = nullptr) {
   const int H = rs.H, G = rs.G, GH = G * H, in = rs.in, Tn = rs.T, bs = rs.bs;
   const bool lstm = rs.cell == TTRNN_LSTM;
   const size_t RROWS = (size_t)rs.B * rs.T;   // reserve layout: res_gate / res_cell
+  // per-sample lengths (include/ttrnn.h, ttrnn_rnn_forward_varlen): the loop runs to the tile's longest sample; a sample past its
+  // own length keeps hbuf / cbuf and writes a zero output row and the frozen record.  lens == nullptr: every sample runs Tn steps
+  int Tmax = Tn;
+  if (lens) {
+    Tmax = 0;
+    for (int s = 0; s < nb; ++s) Tmax = tmax(Tmax, varlen_clamp(lens[b0 + s], Tn));
+  }
+  auto freeze = [&](int e, int j, size_t bt) {
+    if (out) st(out + bt * H, j, 0.f);
+    if (reserve) {
+      float* rv = reserve + res_gate(bt, H, j);
+      if (lstm) {                                 // (i, g, f, o) = (0, 0, 1, 0), c_t = c_{len-1}
+        rv[0] = 0.f; rv[1] = 0.f; rv[2] = 1.f; rv[3] = 0.f;
+        reserve[res_cell(RROWS, bt, H, j)] = cbuf[e];
+      } else {                                    // (r, z, n, hn) = (0, 1, 0, 0)
+        rv[0] = 0.f; rv[1] = 1.f; rv[2] = 0.f; rv[3] = 0.f;
+      }
+    }
+  };
   ex.par([&](int tid, int nthr) {
     for (int e = tid; e < nb * H; e += nthr) {
       const int s = e / H, j = e - s * H;
@@ -553,7 +575,7 @@ TT_HD void rnn_fwd_body(Ex& ex, const RnnShape& rs, int b0, int nb,
       if (lstm) cbuf[e] = c0 ? ld(c0, (size_t)(b0 + s) * H + j) : 0.f;
     }
   });
-  for (int t = 0; t < Tn; ++t) {
+  for (int t = 0; t < Tmax; ++t) {
     // input TTLinear: gin = W_in x_t + b_in
     ex.par([&](int tid, int nthr) {
       for (int e = tid; e < nb * in; e += nthr) {
@@ -585,6 +607,7 @@ TT_HD void rnn_fwd_body(Ex& ex, const RnnShape& rs, int b0, int nb,
         const float* gi = gin + (size_t)s * GH;
         const float* gh = r + (size_t)s * bs;
         const size_t bt = (size_t)(b0 + s) * Tn + t;
+        if (lens && t >= varlen_clamp(lens[b0 + s], Tn)) { freeze(e, j, bt); continue; }
         float hy;
         if (lstm) {
           float p0 = gi[j] + gh[j], p1 = gi[H + j] + gh[H + j];
@@ -615,6 +638,14 @@ TT_HD void rnn_fwd_body(Ex& ex, const RnnShape& rs, int b0, int nb,
         // (out == NULL: the caller consumes only the final state — include/ttrnn.h, ttrnn_rnn_out_optional)
         if (out) st(out + bt * H, j, hy);
         hbuf[e] = round_as(out, hy);
+      }
+    });
+  }
+  if (Tmax < Tn && (out || reserve)) {            // the steps past the tile's longest sample: store only
+    ex.par([&](int tid, int nthr) {
+      for (int e = tid; e < nb * H; e += nthr) {
+        const int s = e / H, j = e - s * H;
+        for (int t = Tmax; t < Tn; ++t) freeze(e, j, (size_t)(b0 + s) * Tn + t);
       }
     });
   }

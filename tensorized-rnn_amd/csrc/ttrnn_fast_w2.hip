@@ -223,6 +223,7 @@ struct W2Args {
   const int* hdr; const _Float16* frag;
   float* out; float* hT; float* cT; float* reserve;
   int B, T;
+  const int* lens;      // per-sample lengths (device, [B]) or NULL: every sample runs T steps (include/ttrnn.h, ttrnn_rnn_forward_varlen)
 };
 
 __device__ __forceinline__ xh8 w2_ld8(const _Float16* p) { return *reinterpret_cast<const xh8*>(p); }
@@ -241,7 +242,8 @@ __device__ __forceinline__ void w2_split8(const float (&v)[8], xh8& p0, xh8& p1)
   p1 = __builtin_bit_cast(xh8, u32x4{b[0], b[1], b[2], b[3]});
 }
 
-template <class S>
+// VL: per-sample lengths (W2Args::lens); a template parameter, so that the fixed-length instantiation is the code it always was
+template <class S, bool VL = false>
 __global__ void __launch_bounds__(256) k_lstm_fwd_w2(W2Args g) {
   constexpr int R = S::R;
   __shared__ __attribute__((aligned(16))) unsigned char smem[S::LDS];
@@ -249,6 +251,7 @@ __global__ void __launch_bounds__(256) k_lstm_fwd_w2(W2Args g) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n = lane & 15, q = lane >> 4;
   const int b = blockIdx.x, T = g.T;
+  const int Tb = VL ? varlen_clamp(g.lens[b], T) : T;      // this sample's steps (workgroup-uniform, read once)
   _Float16* himg = reinterpret_cast<_Float16*>(smem + S::L_H);       // [par][piece][HROWS][HS]
   _Float16* ximg = reinterpret_cast<_Float16*>(smem + S::L_X);       // [par][piece][16][XS]
   int* xexp = reinterpret_cast<int*>(smem + S::L_E);
@@ -354,13 +357,13 @@ __global__ void __launch_bounds__(256) k_lstm_fwd_w2(W2Args g) {
   put_h(0, ldexpf(1.f, 13 - e0));
   float xnext = 0.f;
   if (wave == 0) {
-    put_x(0, (lane < S::INP && T > 0) ? xrow[lane] : 0.f);
-    if (lane < S::INP && T > 1) xnext = xrow[S::INP + lane];
+    put_x(0, (lane < S::INP && Tb > 0) ? xrow[lane] : 0.f);
+    if (lane < S::INP && Tb > 1) xnext = xrow[S::INP + lane];
   }
   __syncthreads();
 
   const size_t rrows = (size_t)g.B * T;
-  for (int t = 0; t < T; ++t) {
+  for (int t = 0; t < Tb; ++t) {
     const int par = t & 1;
     const _Float16* hp = himg + par * 2 * HP;
     const _Float16* xp = ximg + par * 2 * XP;
@@ -448,10 +451,24 @@ __global__ void __launch_bounds__(256) k_lstm_fwd_w2(W2Args g) {
     put_h(par ^ 1, 8192.f);
     if (wave == 0) {
       put_x(par ^ 1, xnext);
-      if (lane < S::INP && t + 2 < T) xnext = xrow[(size_t)(t + 2) * S::INP + lane];
+      if (lane < S::INP && t + 2 < Tb) xnext = xrow[(size_t)(t + 2) * S::INP + lane];
     }
     lds_barrier();
   }
+  // steps past the sample's own length (store only): zero output rows and the frozen record (i, g, f, o) = (0, 0, 1, 0) with
+  // c_t = c_{len-1}, on which the reverse kernels give exact-zero gate gradients and pass dc through (include/ttrnn.h)
+  if (VL && (g.out || g.reserve))
+    for (int t = Tb; t < T; ++t) {
+      const size_t bt = (size_t)b * T + t;
+#pragma unroll
+      for (int tl = 0; tl < S::MT2; ++tl) {
+        if (g.out) g.out[bt * S::H + unit[tl]] = 0.f;
+        if (g.reserve) {
+          *reinterpret_cast<f32x4*>(g.reserve + res_gate(bt, S::H, unit[tl])) = f32x4{0.f, 0.f, 1.f, 0.f};
+          g.reserve[res_cell(rrows, bt, S::H, unit[tl])] = cst[tl];
+        }
+      }
+    }
 #pragma unroll
   for (int tl = 0; tl < S::MT2; ++tl) {
     if (g.hT) g.hT[(size_t)b * S::H + unit[tl]] = hval[tl];
@@ -464,7 +481,7 @@ __global__ void __launch_bounds__(256) k_lstm_fwd_w2(W2Args g) {
 // the n gate.  A caller's h_0 outside (-1, 1) does not decay in one step as an LSTM's does (h' = (1 - z) n + z h): the state image
 // is written under the exponent of the LAST step's exact maximum (a bound on this step's: |h'| <= max(1, |h|)), which every wave
 // leaves in LDS next to the image.
-template <class S>
+template <class S, bool VL = false>
 __global__ void __launch_bounds__(64 * S::NWV) k_gru_fwd_w2(W2Args g) {
   constexpr int R = S::R, NTH = 64 * S::NWV;
   static_assert(S::GATES == 3, "TT-GRU configuration");
@@ -474,6 +491,7 @@ __global__ void __launch_bounds__(64 * S::NWV) k_gru_fwd_w2(W2Args g) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n = lane & 15, q = lane >> 4;
   const int b = blockIdx.x, T = g.T;
+  const int Tb = VL ? varlen_clamp(g.lens[b], T) : T;      // this sample's steps (workgroup-uniform, read once)
   _Float16* himg = reinterpret_cast<_Float16*>(smem + S::L_H);       // [par][piece][HROWS][HS]
   _Float16* ximg = reinterpret_cast<_Float16*>(smem + S::L_X);       // [par][piece][16][XS]
   int* xexp = reinterpret_cast<int*>(smem + S::L_E);
@@ -573,12 +591,12 @@ __global__ void __launch_bounds__(64 * S::NWV) k_gru_fwd_w2(W2Args g) {
   put_h(0, ldexpf(1.f, 13 - e_img));
   float xnext = 0.f;
   if (wave == 0) {
-    put_x(0, (lane < S::INP && T > 0) ? xrow[lane] : 0.f);
-    if (lane < S::INP && T > 1) xnext = xrow[S::INP + lane];
+    put_x(0, (lane < S::INP && Tb > 0) ? xrow[lane] : 0.f);
+    if (lane < S::INP && Tb > 1) xnext = xrow[S::INP + lane];
   }
   __syncthreads();
 
-  for (int t = 0; t < T; ++t) {
+  for (int t = 0; t < Tb; ++t) {
     const int par = t & 1;
     const _Float16* hp = himg + par * 2 * HP;
     const _Float16* xp = ximg + par * 2 * XP;
@@ -677,10 +695,20 @@ __global__ void __launch_bounds__(64 * S::NWV) k_gru_fwd_w2(W2Args g) {
     e_img = e_wr;
     if (wave == 0) {
       put_x(par ^ 1, xnext);
-      if (lane < S::INP && t + 2 < T) xnext = xrow[(size_t)(t + 2) * S::INP + lane];
+      if (lane < S::INP && t + 2 < Tb) xnext = xrow[(size_t)(t + 2) * S::INP + lane];
     }
     lds_barrier();
   }
+  // steps past the sample's own length (store only): zero output rows and the frozen record (r, z, n, hn) = (0, 1, 0, 0)
+  if (VL && (g.out || g.reserve))
+    for (int t = Tb; t < T; ++t) {
+      const size_t bt = (size_t)b * T + t;
+#pragma unroll
+      for (int tl = 0; tl < S::MT2; ++tl) {
+        if (g.out) g.out[bt * S::H + unit[tl]] = 0.f;
+        if (g.reserve) *reinterpret_cast<f32x4*>(g.reserve + res_gate(bt, S::H, unit[tl])) = f32x4{0.f, 1.f, 0.f, 0.f};
+      }
+    }
 #pragma unroll
   for (int tl = 0; tl < S::MT2; ++tl)
     if (g.hT) g.hT[(size_t)b * S::H + unit[tl]] = hval[tl];
@@ -1231,7 +1259,7 @@ int w2_config_gru(const TtShape& hid, const TtShape& in) {
 template <class S>
 static int launch_fwd_w2g_t(const RnnShape& rs, const void* x, const void* h0, const float* packed_in, const void* bias_in,
                             const float* packed_hid, const void* bias_hid, void* out, void* hT, float* reserve, void* ws,
-                            hipStream_t stream, int phase) {
+                            hipStream_t stream, int phase, const int* lens) {
   int* hdr = (int*)ws;
   _Float16* frag = (_Float16*)((char*)ws + S::HDR_BYTES);
   if (phase != TTRNN_PHASE_RUN) {
@@ -1256,15 +1284,16 @@ static int launch_fwd_w2g_t(const RnnShape& rs, const void* x, const void* h0, c
   a.bias_hid = rs.has_bias_hid ? (const float*)bias_hid : nullptr;
   a.hdr = hdr; a.frag = frag;
   a.out = (float*)out; a.hT = (float*)hT; a.cT = nullptr; a.reserve = reserve;
-  a.B = rs.B; a.T = rs.T;
-  hipLaunchKernelGGL(k_gru_fwd_w2<S>, dim3(rs.B), dim3(64 * S::NWV), 0, stream, a);
+  a.B = rs.B; a.T = rs.T; a.lens = lens;
+  if (lens) hipLaunchKernelGGL((k_gru_fwd_w2<S, true>), dim3(rs.B), dim3(64 * S::NWV), 0, stream, a);
+  else hipLaunchKernelGGL(k_gru_fwd_w2<S>, dim3(rs.B), dim3(64 * S::NWV), 0, stream, a);
   return hipGetLastError() == hipSuccess ? TTRNN_OK : TTRNN_ERR_LAUNCH;
 }
 
 template <class S>
 static int launch_fwd_w2_t(const RnnShape& rs, const void* x, const void* h0, const void* c0, const float* packed_in, const void* bias_in,
                            const float* packed_hid, const void* bias_hid, void* out, void* hT, void* cT, float* reserve, void* ws,
-                           hipStream_t stream, int phase) {
+                           hipStream_t stream, int phase, const int* lens) {
   int* hdr = (int*)ws;
   _Float16* frag = (_Float16*)((char*)ws + S::HDR_BYTES);
   if (phase != TTRNN_PHASE_RUN) {
@@ -1289,8 +1318,9 @@ static int launch_fwd_w2_t(const RnnShape& rs, const void* x, const void* h0, co
   a.bias_hid = rs.has_bias_hid ? (const float*)bias_hid : nullptr;
   a.hdr = hdr; a.frag = frag;
   a.out = (float*)out; a.hT = (float*)hT; a.cT = (float*)cT; a.reserve = reserve;
-  a.B = rs.B; a.T = rs.T;
-  hipLaunchKernelGGL(k_lstm_fwd_w2<S>, dim3(rs.B), dim3(64 * S::NWV), 0, stream, a);
+  a.B = rs.B; a.T = rs.T; a.lens = lens;
+  if (lens) hipLaunchKernelGGL((k_lstm_fwd_w2<S, true>), dim3(rs.B), dim3(64 * S::NWV), 0, stream, a);
+  else hipLaunchKernelGGL(k_lstm_fwd_w2<S>, dim3(rs.B), dim3(64 * S::NWV), 0, stream, a);
   return hipGetLastError() == hipSuccess ? TTRNN_OK : TTRNN_ERR_LAUNCH;
 }
 
@@ -1377,21 +1407,21 @@ size_t w2_rnn_fwd_workspace_bytes() {      // (the query has no shape; the four-
 
 int launch_rnn_fwd_w2(const RnnShape& rs, const void* x, const void* h0, const void* c0, const float* packed_in, const void* bias_in,
                       const float* packed_hid, const void* bias_hid, void* out, void* hT, void* cT, float* reserve, void* ws,
-                      hipStream_t stream, int phase) {
+                      hipStream_t stream, int phase, const int* lens) {
   if (rs.cell == TTRNN_GRU) {
     switch (w2_config_gru(rs.hid_s, rs.in_s)) {
-      case 1: return launch_fwd_w2g_t<W2GA2>(rs, x, h0, packed_in, bias_in, packed_hid, bias_hid, out, hT, reserve, ws, stream, phase);
-      case 2: return launch_fwd_w2g_t<W2GA4>(rs, x, h0, packed_in, bias_in, packed_hid, bias_hid, out, hT, reserve, ws, stream, phase);
-      case 3: return launch_fwd_w2g_t<W2GB2>(rs, x, h0, packed_in, bias_in, packed_hid, bias_hid, out, hT, reserve, ws, stream, phase);
-      case 4: return launch_fwd_w2g_t<W2GB4>(rs, x, h0, packed_in, bias_in, packed_hid, bias_hid, out, hT, reserve, ws, stream, phase);
+      case 1: return launch_fwd_w2g_t<W2GA2>(rs, x, h0, packed_in, bias_in, packed_hid, bias_hid, out, hT, reserve, ws, stream, phase, lens);
+      case 2: return launch_fwd_w2g_t<W2GA4>(rs, x, h0, packed_in, bias_in, packed_hid, bias_hid, out, hT, reserve, ws, stream, phase, lens);
+      case 3: return launch_fwd_w2g_t<W2GB2>(rs, x, h0, packed_in, bias_in, packed_hid, bias_hid, out, hT, reserve, ws, stream, phase, lens);
+      case 4: return launch_fwd_w2g_t<W2GB4>(rs, x, h0, packed_in, bias_in, packed_hid, bias_hid, out, hT, reserve, ws, stream, phase, lens);
     }
     return TTRNN_ERR_UNSUPPORTED;
   }
   switch (w2_config(rs.hid_s, rs.in_s)) {
-    case 1: return launch_fwd_w2_t<W2A2>(rs, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream, phase);
-    case 2: return launch_fwd_w2_t<W2A4>(rs, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream, phase);
-    case 3: return launch_fwd_w2_t<W2B2>(rs, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream, phase);
-    case 4: return launch_fwd_w2_t<W2B4>(rs, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream, phase);
+    case 1: return launch_fwd_w2_t<W2A2>(rs, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream, phase, lens);
+    case 2: return launch_fwd_w2_t<W2A4>(rs, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream, phase, lens);
+    case 3: return launch_fwd_w2_t<W2B2>(rs, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream, phase, lens);
+    case 4: return launch_fwd_w2_t<W2B4>(rs, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream, phase, lens);
   }
   return TTRNN_ERR_UNSUPPORTED;
 }

@@ -424,12 +424,15 @@ __device__ __forceinline__ void split_block_h(const xh8 (&w)[2], const xh8 (&x)[
 // was 384 KB per sample-step through a 64 B/clk L2 -> CU path: 8.7 us per step at B = 512 for 1.3 us of matrix-pipe time
 // IN1: input_size == 1 as a template parameter (round 4, lesson 44: the runtime flag cost the fused-core kernels 9 - 10 %)
 // CIN (round 5, RES only): the unit of a wave is a ROW tile with its N2T <= 4 column tiles inside (G2Mat::cin)
-template <int CELL, typename TS, int UPT, bool RES, bool DIAG, bool P8, int NSL = G2_PF, bool IN1 = false, bool CIN = false>
+// VL: per-sample lengths (`lens`, device [B]; include/ttrnn.h ttrnn_rnn_forward_varlen) — a workgroup-uniform loop bound and a
+// store-only tail, as a template parameter (no per-step flag: lesson 44); VL = false is the kernel as it always was
+template <int CELL, typename TS, int UPT, bool RES, bool DIAG, bool P8, int NSL = G2_PF, bool IN1 = false, bool CIN = false,
+          bool VL = false>
 __global__ void __launch_bounds__(G2_NT_MAX) k_g2_fwd(G2Plan P, GinSrc gs, const float* __restrict__ bilv, const TS* __restrict__ h0,
                                                   const TS* __restrict__ c0, const xh8* __restrict__ fs2,
                                                   const float* __restrict__ ft1, const int* __restrict__ hdr,
                                                   TS* __restrict__ out, TS* __restrict__ hT,
-                                                  TS* __restrict__ cT, float* __restrict__ reserve) {
+                                                  TS* __restrict__ cT, float* __restrict__ reserve, const int* __restrict__ lens) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const G2Mat& m = P.hid;
   _Float16* hb = reinterpret_cast<_Float16*>(smem);                 // stage 1's operand: two fp16 planes of 2^9 h, [2][16*N1T][JS]
@@ -449,6 +452,7 @@ __global__ void __launch_bounds__(G2_NT_MAX) k_g2_fwd(G2Plan P, GinSrc gs, const
   const int NW = m.nw, NT = NW * 64;
   const size_t b = blockIdx.x;
   const int H = P.H, T = P.T, GH = P.G * P.H, upt = P.upt;
+  const int Tb = VL ? varlen_clamp(lens[b], T) : T;                // this sample's steps (workgroup-uniform, read once)
   constexpr bool LSTM = CELL == TTRNN_LSTM;
   const float r1sc = ldexpf(1.f, g2_r1_expo(m.Jt));                 // stage-1 sums -> below 2^15 before they are split
 
@@ -602,7 +606,7 @@ __global__ void __launch_bounds__(G2_NT_MAX) k_g2_fwd(G2Plan P, GinSrc gs, const
   unsigned long long last_ = 0;
   if constexpr (DIAG) last_ = stamp();
 
-  for (int t = 0; t < T; ++t) {
+  for (int t = 0; t < Tb; ++t) {
     const size_t bt = b * T + t;
     // gate inputs of this step: requested now, used after both stages
     // ---- stage 1 (two fp16 pieces): C1 = Gt h, split into the two fp16 planes of stage 2's operand ---------------------------
@@ -865,6 +869,30 @@ __global__ void __launch_bounds__(G2_NT_MAX) k_g2_fwd(G2Plan P, GinSrc gs, const
 #pragma unroll
       for (int i = 0; i < 8; ++i) dst[i] = seg[i];
     }
+  }
+  // steps past the sample's own length (store only): zero output rows and the frozen records — LSTM (i, g, f, o) = (0, 0, 1, 0)
+  // with c_t = c_{len-1}, GRU (r, z, n, hn) = (0, 1, 0, 0) — on which the reverse kernels give exact-zero gate gradients
+  if constexpr (VL) {
+    if (out || reserve)
+      for (int t = Tb; t < T; ++t) {
+        const size_t bt = b * T + t;
+#pragma unroll
+        for (int u = 0; u < UPT; ++u)
+          if (u < upt) {
+            const int hid = tid + u * NT;
+            if (hid < H) {
+              if (out) st(out, bt * H + hid, 0.f);
+              if (reserve) {
+                if (LSTM) {
+                  *reinterpret_cast<f32x4*>(reserve + res_gate(bt, H, hid)) = f32x4{0.f, 0.f, 1.f, 0.f};
+                  reserve[res_cell((size_t)P.B * T, bt, H, hid)] = cst[u];
+                } else {
+                  *reinterpret_cast<f32x4*>(reserve + (bt * H + hid) * 4) = f32x4{0.f, 1.f, 0.f, 0.f};
+                }
+              }
+            }
+          }
+      }
   }
 #pragma unroll
   for (int u = 0; u < UPT; ++u)
@@ -1997,10 +2025,14 @@ struct G2FwdWs {
   size_t gin, bilv, rec, ident, wdense, planes, xpad, lin, total;
 };
 
-static G2FwdWs g2_fwd_layout(const RnnShape& rs) {
+// varlen: the plan of a call with per-sample lengths — one sample per workgroup (k_g2_fwd), never the pair kernel
+static void plan_for_varlen(G2Plan* p, const RnnShape& rs) { plan_for_single(p, rs, false); }
+
+static G2FwdWs g2_fwd_layout(const RnnShape& rs, bool varlen = false) {
   G2FwdWs w{};
   G2Plan p;
-  plan_for(&p, rs, false);
+  if (varlen) plan_for_varlen(&p, rs);
+  else plan_for(&p, rs, false);
   const bool in1 = rs.in == 1;
   const int inp = in_pad(rs.in);
   const int64_t rows = in1 ? 1 : (int64_t)rs.B * rs.T;
@@ -2032,6 +2064,13 @@ static G2FwdWs g2_fwd_layout(const RnnShape& rs) {
 }
 
 size_t g2_rnn_fwd_workspace(const RnnShape& rs) { return g2_fwd_layout(rs).total; }
+size_t g2_rnn_fwd_varlen_workspace(const RnnShape& rs) { return g2_fwd_layout(rs, true).total; }
+bool g2_rnn_varlen_available(const RnnShape& rs, int dtype) {
+  if (!g2_available(rs, dtype, false)) return false;      // (options, dtype, math mode, the K-in GEMM's limits)
+  G2Plan p;
+  plan_for_varlen(&p, rs);
+  return p.hid.ok && p.okf && !p.pair;
+}
 
 size_t g2_rnn_bwd_workspace(const RnnShape& rs) {
   G2Plan p;
@@ -2042,8 +2081,8 @@ size_t g2_rnn_bwd_workspace(const RnnShape& rs) {
 template <typename TS>
 static int fwd_t(const RnnShape& rs, const G2Plan& P, int dtype, const void* x, const void* h0, const void* c0,
                  const float* packed_in, const void* bias_in, const float* packed_hid, const void* bias_hid, void* out,
-                 void* hT, void* cT, float* reserve, void* workspace, hipStream_t stream) {
-  const G2FwdWs L = g2_fwd_layout(rs);
+                 void* hT, void* cT, float* reserve, void* workspace, hipStream_t stream, const int* lens) {
+  const G2FwdWs L = g2_fwd_layout(rs, lens != nullptr);
   char* p = (char*)workspace;
   float* gin = (float*)p; p += L.gin;
   float* bilv = (float*)p; p += L.bilv;
@@ -2111,22 +2150,23 @@ static int fwd_t(const RnnShape& rs, const G2Plan& P, int dtype, const void* x, 
   // the reference's default benchmark shape (H = 512, r = 8) in split mode: the fused-core forward kernel on the gin just built
   // (both biases are folded into it), this tier's `rec` region as its fragment workspace (ttrnn_fast_f10.hip)
   // the fp32 TT-GRU shape with a fused-core forward kernel (H = 256, r = 8; input_size != 1 arrives here): that kernel on this gin
-  if (dtype == TTRNN_F32 && !opt(OPT_FORCE_G2) && f10gh_available(rs, dtype)) {      // (either input size: GinSrc says which)
+  // (a call with per-sample lengths stays on this tier's own kernel: the fused-core forward kernels do not take lengths)
+  if (!lens && dtype == TTRNN_F32 && !opt(OPT_FORCE_G2) && f10gh_available(rs, dtype)) {      // (either input size: GinSrc says which)
     if (L.rec < f10gh_workspace_bytes(rs)) return TTRNN_ERR_WORKSPACE;      // (never: g2_fwd_layout sizes it)
     GinSrc srcg{gin, x, in1 ? 1 : 0};
     return launch_gru_fwd_f10gh_g2(rs, srcg, bilv, h0, packed_hid, out, hT, reserve, rec, stream);
   }
-  if (!in1 && dtype == TTRNN_F32 && !opt(OPT_FORCE_G2) && f10g5_available(rs, dtype)) {      // H = 512, r = 8: gates on the accumulators
+  if (!lens && !in1 && dtype == TTRNN_F32 && !opt(OPT_FORCE_G2) && f10g5_available(rs, dtype)) {      // H = 512, r = 8: gates on the accumulators
     if (L.rec < f10g5_workspace_bytes(rs)) return TTRNN_ERR_WORKSPACE;
     return launch_gru_fwd_f10g5(rs, gin, h0, packed_hid, out, hT, reserve, rec, stream);
   }
   // the naive per-gate TT-LSTM / TT-GRU of H = 256, r = 8: one gate per wave on the fused-core scheme (ttrnn_fast_f10n.hip), either K-in
-  if (dtype == TTRNN_F32 && !opt(OPT_FORCE_G2) && f10n_available(rs, dtype)) {
+  if (!lens && dtype == TTRNN_F32 && !opt(OPT_FORCE_G2) && f10n_available(rs, dtype)) {
     if (L.rec < f10n_workspace_bytes(rs)) return TTRNN_ERR_WORKSPACE;
     GinSrc srcn{gin, x, in1 ? 1 : 0};
     return launch_lstm_fwd_f10n(rs, srcn, bilv, h0, c0, packed_hid, out, hT, cT, reserve, rec, stream);
   }
-  if (f10_h512_fwd_available(rs, dtype)) {
+  if (!lens && f10_h512_fwd_available(rs, dtype)) {
     if (L.rec < f10_h512_workspace_bytes()) return TTRNN_ERR_WORKSPACE;      // (never: g2_fwd_layout sizes it)
     return launch_rnn_fwd_f10_h512(rs, gin, h0, c0, packed_hid, out, hT, cT, reserve, rec, stream);
   }
@@ -2145,6 +2185,7 @@ static int fwd_t(const RnnShape& rs, const G2Plan& P, int dtype, const void* x, 
     hipLaunchKernelGGL(kern, dim3(grid), dim3(G2_NT_MAX), P.f_lds, stream, P, src, bilv, (const TS*)h0, (const TS*)c0,     \
                        reinterpret_cast<const xh8*>(fs2), ft1, hdr, (TS*)out, (TS*)hT, (TS*)cT, reserve);                  \
   } while (0)
+    if (lens) return TTRNN_ERR_UNSUPPORTED;      // (never: plan_for_varlen does not pair)
     const bool dg = opt(OPT_DIAG) && reserve && P.upt == 1 && !in1 && rs.cell == TTRNN_LSTM && std::is_same<TS, float>::value && P.pair == 1;
     if (dg) {
       if constexpr (std::is_same<TS, float>::value) TT_G2_PAIR(TTRNN_LSTM, 1, false, true);
@@ -2160,64 +2201,76 @@ static int fwd_t(const RnnShape& rs, const G2Plan& P, int dtype, const void* x, 
   }
   const bool res = P.hid.UW * P.hid.KBP <= G2_PF;      // head fragments register-resident for every wave
   const bool res16 = g2_fwd_res16(P);                  // ... in sixteen slots (eight-wave workgroups, UPT <= 2)
-#define TT_G2_FWD(CELLV, UPTV, SLOT)                                                                                      \
+#define TT_G2_FWD(CELLV, UPTV, VLV)                                                                                       \
   do {                                                                                                                   \
     const bool p8 = P.hid.pack8 != 0;                                                                                   \
     if (res16 && UPTV <= 2) {                                                                                           \
-      auto kern16 = in1 ? (p8 ? k_g2_fwd<CELLV, TS, (UPTV <= 2 ? UPTV : 1), true, false, true, 16, true>                 \
-                              : k_g2_fwd<CELLV, TS, (UPTV <= 2 ? UPTV : 1), true, false, false, 16, true>)               \
-                        : (p8 ? k_g2_fwd<CELLV, TS, (UPTV <= 2 ? UPTV : 1), true, false, true, 16>                       \
-                              : k_g2_fwd<CELLV, TS, (UPTV <= 2 ? UPTV : 1), true, false, false, 16>);                    \
+      auto kern16 = in1 ? (p8 ? k_g2_fwd<CELLV, TS, (UPTV <= 2 ? UPTV : 1), true, false, true, 16, true, false, VLV>     \
+                              : k_g2_fwd<CELLV, TS, (UPTV <= 2 ? UPTV : 1), true, false, false, 16, true, false, VLV>)   \
+                        : (p8 ? k_g2_fwd<CELLV, TS, (UPTV <= 2 ? UPTV : 1), true, false, true, 16, false, false, VLV>    \
+                              : k_g2_fwd<CELLV, TS, (UPTV <= 2 ? UPTV : 1), true, false, false, 16, false, false, VLV>); \
       if (ensure_dynamic_lds(reinterpret_cast<const void*>(kern16), P.f_lds) != TTRNN_OK) return TTRNN_ERR_LAUNCH;     \
       hipLaunchKernelGGL(kern16, dim3(rs.B), dim3(P.hid.nw * 64), P.f_lds, stream, P, src, bilv, (const TS*)h0,          \
-                         (const TS*)c0, reinterpret_cast<const xh8*>(fs2), ft1, hdr, (TS*)out, (TS*)hT, (TS*)cT, reserve); \
+                         (const TS*)c0, reinterpret_cast<const xh8*>(fs2), ft1, hdr, (TS*)out, (TS*)hT, (TS*)cT, reserve, \
+                         lens);                                                                                          \
       break;                                                                                                             \
     }                                                                                                                    \
     if (P.hid.cin) {                                                                                                     \
-      auto kernc = in1 ? (p8 ? k_g2_fwd<CELLV, TS, UPTV, true, false, true, G2_PF, true, true>                           \
-                             : k_g2_fwd<CELLV, TS, UPTV, true, false, false, G2_PF, true, true>)                         \
-                       : (p8 ? k_g2_fwd<CELLV, TS, UPTV, true, false, true, G2_PF, false, true>                          \
-                             : k_g2_fwd<CELLV, TS, UPTV, true, false, false, G2_PF, false, true>);                       \
+      auto kernc = in1 ? (p8 ? k_g2_fwd<CELLV, TS, UPTV, true, false, true, G2_PF, true, true, VLV>                      \
+                             : k_g2_fwd<CELLV, TS, UPTV, true, false, false, G2_PF, true, true, VLV>)                    \
+                       : (p8 ? k_g2_fwd<CELLV, TS, UPTV, true, false, true, G2_PF, false, true, VLV>                     \
+                             : k_g2_fwd<CELLV, TS, UPTV, true, false, false, G2_PF, false, true, VLV>);                  \
       if (ensure_dynamic_lds(reinterpret_cast<const void*>(kernc), P.f_lds) != TTRNN_OK) return TTRNN_ERR_LAUNCH;      \
       hipLaunchKernelGGL(kernc, dim3(rs.B), dim3(P.hid.nw * 64), P.f_lds, stream, P, src, bilv, (const TS*)h0,           \
-                         (const TS*)c0, reinterpret_cast<const xh8*>(fs2), ft1, hdr, (TS*)out, (TS*)hT, (TS*)cT, reserve); \
+                         (const TS*)c0, reinterpret_cast<const xh8*>(fs2), ft1, hdr, (TS*)out, (TS*)hT, (TS*)cT, reserve, \
+                         lens);                                                                                          \
       break;                                                                                                             \
     }                                                                                                                    \
-    const bool dg = opt(OPT_DIAG) && reserve && UPTV == 1 && res && !in1;                                               \
-    auto kern = dg ? (p8 ? k_g2_fwd<CELLV, TS, UPTV, true, true, true> : k_g2_fwd<CELLV, TS, UPTV, true, true, false>)   \
-              : in1 ? (res ? (p8 ? k_g2_fwd<CELLV, TS, UPTV, true, false, true, G2_PF, true>                             \
-                                 : k_g2_fwd<CELLV, TS, UPTV, true, false, false, G2_PF, true>)                           \
-                           : (p8 ? k_g2_fwd<CELLV, TS, UPTV, false, false, true, G2_PF, true>                            \
-                                 : k_g2_fwd<CELLV, TS, UPTV, false, false, false, G2_PF, true>))                         \
-              : (res ? (p8 ? k_g2_fwd<CELLV, TS, UPTV, true, false, true> : k_g2_fwd<CELLV, TS, UPTV, true, false, false>) \
-                     : (p8 ? k_g2_fwd<CELLV, TS, UPTV, false, false, true> : k_g2_fwd<CELLV, TS, UPTV, false, false, false>)); \
+    /* (the stamped DIAG instantiations are fixed-length only) */                                                        \
+    const bool dg = !VLV && opt(OPT_DIAG) && reserve && UPTV == 1 && res && !in1;                                       \
+    auto kern = dg ? (p8 ? k_g2_fwd<CELLV, TS, UPTV, true, !VLV, true, G2_PF, false, false, VLV>                         \
+                         : k_g2_fwd<CELLV, TS, UPTV, true, !VLV, false, G2_PF, false, false, VLV>)                       \
+              : in1 ? (res ? (p8 ? k_g2_fwd<CELLV, TS, UPTV, true, false, true, G2_PF, true, false, VLV>                 \
+                                 : k_g2_fwd<CELLV, TS, UPTV, true, false, false, G2_PF, true, false, VLV>)               \
+                           : (p8 ? k_g2_fwd<CELLV, TS, UPTV, false, false, true, G2_PF, true, false, VLV>                \
+                                 : k_g2_fwd<CELLV, TS, UPTV, false, false, false, G2_PF, true, false, VLV>))             \
+              : (res ? (p8 ? k_g2_fwd<CELLV, TS, UPTV, true, false, true, G2_PF, false, false, VLV>                      \
+                           : k_g2_fwd<CELLV, TS, UPTV, true, false, false, G2_PF, false, false, VLV>)                    \
+                     : (p8 ? k_g2_fwd<CELLV, TS, UPTV, false, false, true, G2_PF, false, false, VLV>                     \
+                           : k_g2_fwd<CELLV, TS, UPTV, false, false, false, G2_PF, false, false, VLV>));                 \
     if (ensure_dynamic_lds(reinterpret_cast<const void*>(kern), P.f_lds) != TTRNN_OK) return TTRNN_ERR_LAUNCH;        \
     hipLaunchKernelGGL(kern, dim3(rs.B), dim3(P.hid.nw * 64), P.f_lds, stream, P, src, bilv, (const TS*)h0, (const TS*)c0,       \
                        reinterpret_cast<const xh8*>(fs2), ft1, hdr, (TS*)out, (TS*)hT,                                   \
-                       (TS*)cT, reserve);                                                                                 \
+                       (TS*)cT, reserve, lens);                                                                           \
+  } while (0)
+#define TT_G2_FWD_CELL(CELLV, VLV)                      \
+  do {                                                  \
+    if (P.upt == 1) TT_G2_FWD(CELLV, 1, VLV);           \
+    else if (P.upt == 2) TT_G2_FWD(CELLV, 2, VLV);      \
+    else TT_G2_FWD(CELLV, 4, VLV);                      \
   } while (0)
   if (rs.cell == TTRNN_LSTM) {
-    if (P.upt == 1) TT_G2_FWD(TTRNN_LSTM, 1, 0);
-    else if (P.upt == 2) TT_G2_FWD(TTRNN_LSTM, 2, 1);
-    else TT_G2_FWD(TTRNN_LSTM, 4, 2);
+    if (lens) TT_G2_FWD_CELL(TTRNN_LSTM, true);
+    else TT_G2_FWD_CELL(TTRNN_LSTM, false);
   } else {
-    if (P.upt == 1) TT_G2_FWD(TTRNN_GRU, 1, 0);
-    else if (P.upt == 2) TT_G2_FWD(TTRNN_GRU, 2, 1);
-    else TT_G2_FWD(TTRNN_GRU, 4, 2);
+    if (lens) TT_G2_FWD_CELL(TTRNN_GRU, true);
+    else TT_G2_FWD_CELL(TTRNN_GRU, false);
   }
+#undef TT_G2_FWD_CELL
 #undef TT_G2_FWD
   return check();
 }
 
 int launch_rnn_fwd_g2(const RnnShape& rs, int dtype, const void* x, const void* h0, const void* c0, const float* packed_in,
                       const void* bias_in, const float* packed_hid, const void* bias_hid, void* out, void* hT, void* cT,
-                      float* reserve, void* workspace, hipStream_t stream) {
+                      float* reserve, void* workspace, hipStream_t stream, const int* lens) {
   G2Plan P;
-  plan_for(&P, rs, false);
-  if (!P.okf) return TTRNN_ERR_UNSUPPORTED;
+  if (lens) plan_for_varlen(&P, rs);
+  else plan_for(&P, rs, false);
+  if (!P.okf || (lens && P.pair)) return TTRNN_ERR_UNSUPPORTED;
   return dtype == TTRNN_F32
-             ? fwd_t<float>(rs, P, dtype, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, workspace, stream)
-             : fwd_t<bf16_t>(rs, P, dtype, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, workspace, stream);
+             ? fwd_t<float>(rs, P, dtype, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, workspace, stream, lens)
+             : fwd_t<bf16_t>(rs, P, dtype, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, workspace, stream, lens);
 }
 
 template <typename TS>

@@ -324,7 +324,7 @@ template <typename T, bool W_LDS, bool BUF_GLOBAL>
 __global__ void __launch_bounds__(NT_RNN) k_rnn_fwd(RnnShape rs, int nb, const T* x, const T* h0, const T* c0,
                                                     const float* packed_in, const T* bias_in,
                                                     const float* packed_hid, const T* bias_hid,
-                                                    T* out, T* hT, T* cT, float* reserve, float* ws) {
+                                                    T* out, T* hT, T* cT, float* reserve, float* ws, const int* lens) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   DevExec ex;
   const int b0 = blockIdx.x * nb;
@@ -348,7 +348,7 @@ __global__ void __launch_bounds__(NT_RNN) k_rnn_fwd(RnnShape rs, int nb, const T
     __syncthreads();
   }
   rnn_fwd_body<DevExec, T>(ex, rs, b0, n, x, h0, c0, Win, rs.has_bias_in ? bias_in : nullptr, Whid,
-                           rs.has_bias_hid ? bias_hid : nullptr, out, hT, cT, reserve, bufA, bufB, hbuf, cbuf, gin);
+                           rs.has_bias_hid ? bias_hid : nullptr, out, hT, cT, reserve, bufA, bufB, hbuf, cbuf, gin, lens);
 }
 
 template <typename T, bool W_LDS, bool BUF_GLOBAL>
@@ -615,14 +615,14 @@ RnnPlan plan_rnn_generic(const RnnShape& rs, bool backward) {
 template <typename T>
 static int launch_rnn_fwd_t(const RnnShape& rs, const RnnPlan& p, const void* x, const void* h0, const void* c0,
                             const float* packed_in, const void* bias_in, const float* packed_hid, const void* bias_hid,
-                            void* out, void* hT, void* cT, float* reserve, void* ws, hipStream_t stream) {
+                            void* out, void* hT, void* cT, float* reserve, void* ws, hipStream_t stream, const int* lens) {
 #define TT_LAUNCH(WL, BG)                                                                                          \
   do {                                                                                                             \
     auto kern = k_rnn_fwd<T, WL, BG>;                                                                              \
     if (set_lds(kern, p.lds_bytes) != TTRNN_OK) return TTRNN_ERR_LAUNCH;                                           \
     hipLaunchKernelGGL(kern, dim3(p.grid), dim3(NT_RNN), p.lds_bytes, stream, rs, p.nb, (const T*)x, (const T*)h0, \
                        (const T*)c0, packed_in, (const T*)bias_in, packed_hid, (const T*)bias_hid, (T*)out,        \
-                       (T*)hT, (T*)cT, reserve, (float*)ws);                                                       \
+                       (T*)hT, (T*)cT, reserve, (float*)ws, lens);                                                 \
   } while (0)
   if (p.w_lds && !p.buf_global) TT_LAUNCH(true, false);
   else if (!p.w_lds && !p.buf_global) TT_LAUNCH(false, false);
@@ -635,10 +635,10 @@ static int launch_rnn_fwd_t(const RnnShape& rs, const RnnPlan& p, const void* x,
 int launch_rnn_fwd_generic(const RnnShape& rs, const RnnPlan& p, int dtype, const void* x, const void* h0,
                            const void* c0, const float* packed_in, const void* bias_in, const float* packed_hid,
                            const void* bias_hid, void* out, void* hT, void* cT, float* reserve, void* ws,
-                           hipStream_t stream) {
+                           hipStream_t stream, const int* lens) {
   return dtype == TTRNN_F32
-             ? launch_rnn_fwd_t<float>(rs, p, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream)
-             : launch_rnn_fwd_t<bf16_t>(rs, p, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream);
+             ? launch_rnn_fwd_t<float>(rs, p, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream, lens)
+             : launch_rnn_fwd_t<bf16_t>(rs, p, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, ws, stream, lens);
 }
 
 template <typename T>

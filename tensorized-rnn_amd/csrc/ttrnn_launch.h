@@ -105,7 +105,7 @@ int launch_ttlinear_bwd(const TtShape& s, const LinPlan& p, int dtype, int dy_dt
 int launch_rnn_fwd_generic(const RnnShape& rs, const RnnPlan& p, int dtype, const void* x, const void* h0,
                            const void* c0, const float* packed_in, const void* bias_in, const float* packed_hid,
                            const void* bias_hid, void* out, void* hT, void* cT, float* reserve, void* ws,
-                           hipStream_t stream);
+                           hipStream_t stream, const int* lens = nullptr);      // lens: per-sample lengths (device, [B]) or NULL
 int launch_rnn_bwd_generic(const RnnShape& rs, const RnnPlan& p, int dtype, const void* out, const void* h0,
                            const void* c0, const float* packed_hid, const float* reserve, const void* d_out,
                            const void* d_hT, const void* d_cT, float* dg_in, float* dg_hid, void* d_h0, void* d_c0,
@@ -306,7 +306,11 @@ size_t g2_rnn_fwd_workspace(const RnnShape& rs);
 size_t g2_rnn_bwd_workspace(const RnnShape& rs);
 int launch_rnn_fwd_g2(const RnnShape& rs, int dtype, const void* x, const void* h0, const void* c0, const float* packed_in,
                       const void* bias_in, const float* packed_hid, const void* bias_hid, void* out, void* hT, void* cT,
-                      float* reserve, void* workspace, hipStream_t stream);
+                      float* reserve, void* workspace, hipStream_t stream, const int* lens = nullptr);
+// per-sample lengths (lens: device, [B]): always k_g2_fwd itself on the unpaired plan — never k_g2_fwd_p, never one of the fused-core
+// forward kernels that take over some of this tier's shapes; the workspace is sized for that plan
+bool g2_rnn_varlen_available(const RnnShape& rs, int dtype);
+size_t g2_rnn_fwd_varlen_workspace(const RnnShape& rs);
 int launch_rnn_bwd_g2(const RnnShape& rs, int dtype, const void* out, const void* h0, const void* c0, const float* packed_hid,
                       const float* reserve, const void* d_out, const void* d_hT, const void* d_cT, float* dg_in,
                       float* dg_hid, void* d_h0, void* d_c0, void* ws, hipStream_t stream, float* dstate = nullptr,
@@ -394,7 +398,10 @@ bool w2_rnn_fwd_available(const RnnShape& rs, int dtype);
 size_t w2_rnn_fwd_workspace_bytes();
 int launch_rnn_fwd_w2(const RnnShape& rs, const void* x, const void* h0, const void* c0, const float* packed_in, const void* bias_in,
                       const float* packed_hid, const void* bias_hid, void* out, void* hT, void* cT, float* reserve, void* ws,
-                      hipStream_t stream, int phase = 0 /* TTRNN_PHASE_ALL */);
+                      hipStream_t stream, int phase = 0 /* TTRNN_PHASE_ALL */, const int* lens = nullptr /* device, [B], or NULL */);
+// d_out_seeded[b][t] = (t < len_b ? d_out[b][t] : 0) + (t == len_b - 1 ? d_hT[b] : 0), storage dtype (ttrnn_fast_varlen.hip)
+int launch_varlen_seed_dout(int dtype, int B, int T, int H, const int* lens, const void* d_out, const void* d_hT, void* d_out_seeded,
+                            hipStream_t stream);
 
 bool w2_rnn_bwd_available(const RnnShape& rs, int dtype);
 size_t w2_rnn_bwd_workspace_bytes();

@@ -81,20 +81,25 @@ class FusedCellMixin(object):
         res = F.tt_rnn_layer(self._layer_spec(), x.unsqueeze(1), hx, cx, cin, bin_, chid, bhid)
         return res[1:]          # (hy, cy) or (hy,)
 
-    def _run_sequence(self, seq, h0, c0=None, need_out=True, x_bounded=False):
+    def _run_sequence(self, seq, h0, c0=None, need_out=True, x_bounded=False, lengths=None):
         from ttrnn_hip import functional as F
         cin, bin_, chid, bhid = self._operands()
         stats = None
         if getattr(self, '_h_logger', None) is not None:       # log_grads=True: per-step statistics from the fused call
+            if lengths is not None:
+                raise ValueError("log_grads=True cannot be combined with lengths: the per-step statistics would include "
+                                 "the frozen steps of the shorter samples")
             stats = F.StepStats(self._h_logger, getattr(self, '_c_logger', None))
         prep = getattr(self, '_prepared', None)
-        if prep is not None and not torch.is_grad_enabled():
+        if lengths is not None:
+            prep = None                                         # a call with lengths takes the unprepared path
+        elif prep is not None and not torch.is_grad_enabled():
             if not prep.fresh():                                # parameters were updated in place since: prepare again
                 prep = self._prepare()
         else:
             prep = None
         return F.tt_rnn_layer(self._layer_spec(), seq, h0, c0, cin, bin_, chid, bhid, stats=stats, prepared=prep,
-                              need_out=need_out, x_bounded=x_bounded)
+                              need_out=need_out, x_bounded=x_bounded, lengths=lengths)
 
     def _prepare(self):
         """(Re)build the weight-only state of this cell for no-grad forwards (ttrnn_hip.functional.PreparedLayer)."""
@@ -237,7 +242,23 @@ class FusedRnnBase(nn.Module):
         # cells with foreign weight types, or a joint matrix with more cores than the library takes, are stepped
         return any(not cell._fusable() for cell in self._all_layers)
 
-    def _forward_fused(self, input, h0, c0, need_outputs=True):
+    def _device_lengths(self, input, lengths):
+        """`lengths` of a forward call as ONE int32 device tensor for all layers (validated here when it comes from the host:
+        ttrnn_hip.functional.device_lengths), or None."""
+        if lengths is None:
+            return None
+        if self.log_grads:
+            raise ValueError("log_grads=True cannot be combined with lengths: the per-step statistics would include the "
+                             "frozen steps of the shorter samples")
+        if self._needs_stepping():
+            raise NotImplementedError("lengths need cells the library runs as whole sequences (nn.Linear, TTLinear or "
+                                      "TTLinearSet weights)")
+        if input.dim() != 3:
+            raise ValueError("expected input of shape (batch, seq_len, input_size), got {}".format(tuple(input.shape)))
+        from ttrnn_hip import functional as F
+        return F.device_lengths(lengths, input.shape[0], input.shape[1], input.device)
+
+    def _forward_fused(self, input, h0, c0, need_outputs=True, lengths=None):
         seq = input
         last = None
         n = len(self._all_layers)
@@ -246,7 +267,7 @@ class FusedRnnBase(nn.Module):
             # a stacked layer's input is the hidden-state sequence below: |x| <= 1 (LSTM: o * tanh(c); GRU: convex combinations
             # of tanh values and h_{t-1}, from |h_0| <= 1 on) — the weight-gradient step then skips its column-maximum pass
             bounded = i > 0 and (self.kind == 'lstm' or h0 is None)
-            last = cell._run_sequence(seq, h0, c0, need_out=need_outputs or i + 1 < n, x_bounded=bounded)
+            last = cell._run_sequence(seq, h0, c0, need_out=need_outputs or i + 1 < n, x_bounded=bounded, lengths=lengths)
             seq = last[0]
         return last
 

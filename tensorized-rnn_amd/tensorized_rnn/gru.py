@@ -72,20 +72,23 @@ class GRU(FusedRnnBase):
     def init_hidden(self, batch_size):
         return torch.zeros(batch_size, self.hidden_size).to(self.device)
 
-    def forward(self, input, init_states=None, need_outputs=True):
+    def forward(self, input, init_states=None, need_outputs=True, lengths=None):
         """
         :param input:       (batch_size, seq_len, input_size)
         :param init_states: optional h (batch_size, hidden_size); seeds every layer.
         :param need_outputs: extension to the reference's signature (as LSTM.forward): False under torch.no_grad() tells the
                  last layer that only the final state is consumed (mnist_classifier.py:52-55 classifies the last step) —
                  `outputs` is then None and the [B, T, H] store is skipped.
+        :param lengths: extension to the reference's signature (as LSTM.forward): one sequence length per sample of a batch
+                 padded to seq_len — outputs[b, t] = 0 for t >= lengths[b], h is the state after the sample's own last step.
         :return: outputs (batch_size, seq_len, hidden_size) of the last layer and its final h.
         """
+        lengths = self._device_lengths(input, lengths)
         if self._needs_stepping():
             h = self.init_hidden(input.shape[0]) if init_states is None else init_states
             outputs, hT, _ = self._forward_stepwise(input, h.to(input.dtype), None)
         else:
-            outputs, hT = self._forward_fused(input, init_states, None, need_outputs)
+            outputs, hT = self._forward_fused(input, init_states, None, need_outputs, lengths)
         return outputs, hT
 
 

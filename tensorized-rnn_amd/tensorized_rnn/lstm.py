@@ -81,21 +81,30 @@ class LSTM(FusedRnnBase):
         c = torch.zeros(batch_size, self.hidden_size).to(self.device)
         return h, c
 
-    def forward(self, input, init_states=None, need_outputs=True):
+    def forward(self, input, init_states=None, need_outputs=True, lengths=None):
         """
         :param input:       (batch_size, seq_len, input_size)
         :param init_states: optional (h, c), each (batch_size, hidden_size); seeds every layer.
         :param need_outputs: extension to the reference's signature.  False under torch.no_grad() tells the last layer that
                  only the final state is consumed (speaker_encoder.py:80-86): `outputs` is then None where the kernel can skip
                  the [B, T, H] store, and the usual tensor everywhere else (and always when autograd is recording).
+        :param lengths: extension to the reference's signature: one sequence length per sample for a batch padded to seq_len
+                 (the reference embeds utterances of different lengths one call at a time, encoder/inference.py:110-154).
+                 Sample b then behaves exactly like that sample run alone on input[b, :lengths[b]]: outputs[b, t] = 0 for
+                 t >= lengths[b] (as pad_packed_sequence pads), and (h, c) are the states after its own last step; every
+                 layer uses the same lengths.  A list, numpy array or CPU tensor is checked (one per sample, 1 <= len <=
+                 seq_len, else ValueError) and uploaded once; an integer tensor on the device is used as it is, without a
+                 synchronisation (graph capture).  The padded input rows never influence a result but must be finite.
+                 Not available with log_grads=True; a prepared module takes its unprepared path.
         :return: outputs (batch_size, seq_len, hidden_size) of the last layer, and that layer's
                  final (h, c), each (batch_size, hidden_size).
         """
+        lengths = self._device_lengths(input, lengths)
         if self._needs_stepping():
             h, c = self.init_hidden(input.shape[0]) if init_states is None else init_states
             h, c = h.to(input.dtype), c.to(input.dtype)
             outputs, hT, cT = self._forward_stepwise(input, h, c)
         else:
             h, c = (None, None) if init_states is None else init_states
-            outputs, hT, cT = self._forward_fused(input, h, c, need_outputs)
+            outputs, hT, cT = self._forward_fused(input, h, c, need_outputs, lengths)
         return outputs, (hT, cT)

@@ -98,6 +98,11 @@ _SIGNATURES = {
                                                ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64), _P,
                                                ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64), _P,
                                                _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    # per-sample sequence lengths (TTRNN_HAS_VARLEN): desc, lengths, then ttrnn_rnn_forward's arguments
+    "ttrnn_rnn_forward_varlen_route": (ctypes.c_int, [ctypes.POINTER(RnnDesc)]),
+    "ttrnn_rnn_varlen_workspace": (ctypes.c_size_t, [ctypes.POINTER(RnnDesc)]),
+    "ttrnn_rnn_forward_varlen": (ctypes.c_int, [ctypes.POINTER(RnnDesc)] + [_P] * 13 + [ctypes.c_size_t, _P]),
+    "ttrnn_rnn_varlen_seed_dout": (ctypes.c_int, [ctypes.POINTER(RnnDesc), _P, _P, _P, _P, _P]),
     "ttrnn_rnn_backward_workspace": (ctypes.c_size_t, [ctypes.POINTER(RnnDesc)]),
     "ttrnn_rnn_backward_workspace_ex": (ctypes.c_size_t, [ctypes.POINTER(RnnDesc), ctypes.c_int]),
     "ttrnn_rnn_backward_route": (ctypes.c_int, [ctypes.POINTER(RnnDesc), ctypes.c_int]),

@@ -368,6 +368,7 @@ class RnnLayerSpec(object):
         self.has_bias_in = bool(has_bias_in)
         self.has_bias_hid = bool(has_bias_hid)
         self.recording = True       # set per call by tt_rnn_layer: is autograd recording?
+        self.lengths = None         # set per call by tt_rnn_layer: per-sample lengths (int32[B] on the device) or None
         gh = self.n_gates * self.hidden_size
         if in_spec.in_features != self.input_size or hid_spec.in_features != self.hidden_size or \
                 in_spec.out_features != gh or hid_spec.out_features != gh:
@@ -414,13 +415,29 @@ class _TTRnnLayerFn(torch.autograd.Function):
         reserve = None
         if need_grad or (stats is not None and spec.cell == "lstm"):      # the per-step c_t live in the reserve records
             reserve = _alloc((lib.ttrnn_rnn_reserve_bytes(ctypes.byref(desc)) // 4,), torch.float32, dev)
-        wsb = lib.ttrnn_rnn_workspace(ctypes.byref(desc))
-        ws = _workspace(wsb, dev)
-        with _timed("ttrnn_rnn_forward"):
-            check(lib.ttrnn_rnn_forward_cores(ctypes.byref(desc), _ptr(x), _ptr(h0), _ptr(c0), ptrs_in, strides_in,
-                                              _ptr(bias_in), ptrs_hid, strides_hid, _ptr(bias_hid), _ptr(packed_in),
-                                              _ptr(packed_hid), _ptr(out), _ptr(hT), _ptr(cT), _ptr(reserve), _ptr(ws), wsb,
-                                              _stream(x)), "ttrnn_rnn_forward_cores")
+        lengths = spec.lengths       # set per call by tt_rnn_layer, like `recording`: int32[B] on the device, or None
+        if lengths is None:
+            wsb = lib.ttrnn_rnn_workspace(ctypes.byref(desc))
+            ws = _workspace(wsb, dev)
+            with _timed("ttrnn_rnn_forward"):
+                check(lib.ttrnn_rnn_forward_cores(ctypes.byref(desc), _ptr(x), _ptr(h0), _ptr(c0), ptrs_in, strides_in,
+                                                  _ptr(bias_in), ptrs_hid, strides_hid, _ptr(bias_hid), _ptr(packed_in),
+                                                  _ptr(packed_hid), _ptr(out), _ptr(hT), _ptr(cT), _ptr(reserve), _ptr(ws),
+                                                  wsb, _stream(x)), "ttrnn_rnn_forward_cores")
+        else:
+            # per-sample lengths (include/ttrnn.h, TTRNN_HAS_VARLEN): pack, then the variable-length forward — zero rows and
+            # frozen records past every sample's own length
+            check(lib.ttrnn_pack_cores2(ctypes.byref(spec.in_spec.desc), ptrs_in, strides_in, _ptr(packed_in),
+                                        ctypes.byref(spec.hid_spec.desc), ptrs_hid, strides_hid, _ptr(packed_hid),
+                                        _dtype_code(x), _stream(x)), "ttrnn_pack_cores2")
+            wsb = lib.ttrnn_rnn_varlen_workspace(ctypes.byref(desc))
+            ws = _workspace(wsb, dev)
+            with _timed("ttrnn_rnn_forward"):
+                check(lib.ttrnn_rnn_forward_varlen(ctypes.byref(desc), _ptr(lengths), _ptr(x), _ptr(h0), _ptr(c0),
+                                                   _ptr(packed_in), _ptr(bias_in), _ptr(packed_hid), _ptr(bias_hid), _ptr(out),
+                                                   _ptr(hT), _ptr(cT), _ptr(reserve), _ptr(ws), wsb, _stream(x)),
+                      "ttrnn_rnn_forward_varlen")
+        ctx.lengths = lengths
         if stats is not None:
             # LSTM reserve: gates [B][T][H][4], then the cell states [B][T][H] (ttrnn_core.h: res_gate / res_cell)
             stats.forward(out, reserve[4 * B * T * H:].view(B, T, H) if spec.cell == "lstm" else None)
@@ -461,6 +478,15 @@ class _TTRnnLayerFn(torch.autograd.Function):
         d_out = d_out.contiguous() if d_out is not None else None
         d_hT = d_hT.contiguous() if d_hT is not None else None
         d_cT = d_cT.contiguous() if d_cT is not None else None
+        if ctx.lengths is not None:
+            # the gradient of hT enters at every sample's own last row, gradients of padded rows are dropped; from here on the
+            # frozen records make the unchanged reverse-time and weight-gradient kernels do the rest (include/ttrnn.h)
+            seeded = _alloc((B, T, H), x.dtype, dev)
+            d_out = d_out.to(x.dtype) if d_out is not None else None
+            d_hT = d_hT.to(x.dtype) if d_hT is not None else None
+            check(lib.ttrnn_rnn_varlen_seed_dout(ctypes.byref(desc), _ptr(ctx.lengths), _ptr(d_out), _ptr(d_hT), _ptr(seeded),
+                                                 _stream(x)), "ttrnn_rnn_varlen_seed_dout")
+            d_out, d_hT = seeded, None
         dg_in = _alloc((B, T, G * H), torch.float32, dev)
         dg_hid = _alloc((B, T, G * H), torch.float32, dev) if spec.cell == "gru" else dg_in
         need = ctx.needs_input_grad
@@ -648,12 +674,14 @@ def _rnn_forward_prepared(spec, x, h0, c0, bias_in, bias_hid, prep, need_out=Tru
     return (out, hT, cT) if spec.cell == "lstm" else (out, hT)
 
 
-def rnn_route(spec, batch, seq_len, dtype=torch.float32):
-    """Name of the kernel family ttrnn_rnn_forward runs for this layer at this size ("fused_core", "runtime_mfma", "valu", ...)."""
+def rnn_route(spec, batch, seq_len, dtype=torch.float32, varlen=False):
+    """Name of the kernel family ttrnn_rnn_forward runs for this layer at this size ("fused_core", "runtime_mfma", "valu", ...);
+    varlen=True: the family ttrnn_rnn_forward_varlen runs (a call with per-sample lengths)."""
     desc = spec.desc(batch, seq_len, _DT[dtype])
-    code = _lib.load().ttrnn_rnn_forward_route(ctypes.byref(desc))
+    lib = _lib.load()
+    code = (lib.ttrnn_rnn_forward_varlen_route if varlen else lib.ttrnn_rnn_forward_route)(ctypes.byref(desc))
     if code < 0:
-        check(code, "ttrnn_rnn_forward_route")
+        check(code, "ttrnn_rnn_forward_varlen_route" if varlen else "ttrnn_rnn_forward_route")
     return _lib.ROUTES[code]
 
 
@@ -718,8 +746,9 @@ class StepStats(object):
                 lg.log_grad.appendleft(b)
 
 
-def _rnn_forward_nograd(spec, x, h0, c0, cores_in, bias_in, cores_hid, bias_hid, need_out):
-    """No-grad forward without the autograd Function (nothing is saved): lets the last layer skip `out` where the route can."""
+def _rnn_forward_nograd(spec, x, h0, c0, cores_in, bias_in, cores_hid, bias_hid, need_out, lengths=None):
+    """No-grad forward without the autograd Function (nothing is saved): lets the last layer skip `out` where the route can.
+    lengths: int32[B] on the device or None (ttrnn_rnn_forward_varlen)."""
     lib = _lib.load()
     B, T, _ = x.shape
     H = spec.hidden_size
@@ -730,6 +759,14 @@ def _rnn_forward_nograd(spec, x, h0, c0, cores_in, bias_in, cores_hid, bias_hid,
     out = _alloc((B, T, H), x.dtype, dev) if want_out else None
     hT = _alloc((B, H), x.dtype, dev)
     cT = _alloc((B, H), x.dtype, dev) if spec.cell == "lstm" else None
+    if lengths is not None:
+        wsb = lib.ttrnn_rnn_varlen_workspace(ctypes.byref(desc))
+        ws = _workspace(wsb, dev)
+        with _timed("ttrnn_rnn_forward"):
+            check(lib.ttrnn_rnn_forward_varlen(ctypes.byref(desc), _ptr(lengths), _ptr(x), _ptr(h0), _ptr(c0), _ptr(packed_in),
+                                               _ptr(bias_in), _ptr(packed_hid), _ptr(bias_hid), _ptr(out), _ptr(hT), _ptr(cT),
+                                               ctypes.c_void_p(0), _ptr(ws), wsb, _stream(x)), "ttrnn_rnn_forward_varlen")
+        return (out, hT, cT) if spec.cell == "lstm" else (out, hT)
     wsb = lib.ttrnn_rnn_workspace(ctypes.byref(desc))
     ws = _workspace(wsb, dev)
     with _timed("ttrnn_rnn_forward"):
@@ -739,8 +776,32 @@ def _rnn_forward_nograd(spec, x, h0, c0, cores_in, bias_in, cores_hid, bias_hid,
     return (out, hT, cT) if spec.cell == "lstm" else (out, hT)
 
 
+def device_lengths(lengths, batch, seq_len, device):
+    """Per-sample lengths as the library wants them: a contiguous int32[batch] tensor on `device`.
+    A list, numpy array or CPU tensor is validated (count, 1 <= len <= seq_len: ValueError) and uploaded; an integer tensor
+    already on the device is used without validation or synchronisation (graph capture) — the kernels clamp for memory
+    safety, and an out-of-range value is the caller's error, confined to that sample."""
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if lengths.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8) or lengths.dim() != 1 \
+                or lengths.shape[0] != batch:
+            raise ValueError("lengths must be an integer tensor of shape ({},), got {} {}".format(
+                batch, lengths.dtype, tuple(lengths.shape)))
+        if lengths.device != device:
+            raise _lib.TtrnnError("lengths is on {} but the input is on {}".format(lengths.device, device))
+        return lengths if (lengths.dtype == torch.int32 and lengths.is_contiguous()) else lengths.to(torch.int32).contiguous()
+    host = torch.as_tensor(lengths)
+    if host.dim() != 1 or host.shape[0] != batch:
+        raise ValueError("lengths must hold one length per sample ({}), got shape {}".format(batch, tuple(host.shape)))
+    if host.is_floating_point() or host.dtype == torch.bool:
+        raise ValueError("lengths must be integers, got {}".format(host.dtype))
+    if batch > 0 and (int(host.min()) < 1 or int(host.max()) > seq_len):
+        raise ValueError("every length must lie in [1, {}] (the padded sequence length), got min {} max {}".format(
+            seq_len, int(host.min()), int(host.max())))
+    return host.to(torch.int32).contiguous().to(device)
+
+
 def tt_rnn_layer(spec, x, h0, c0, cores_in, bias_in, cores_hid, bias_hid, stats=None, prepared=None, need_out=True,
-                 x_bounded=False):
+                 x_bounded=False, lengths=None):
     """One recurrent layer over the whole sequence on the device.
     Returns (out[B,T,H], hT[B,H], cT[B,H]) for LSTM and (out, hT) for GRU.
     stats: optional StepStats — ActivGradLogger's per-step statistics without leaving the fused path.
@@ -748,7 +809,12 @@ def tt_rnn_layer(spec, x, h0, c0, cores_in, bias_in, cores_hid, bias_hid, stats=
     need_out=False (no-grad calls only): the caller consumes only the final state; `out` is returned as None where the
     route can skip it (include/ttrnn.h: ttrnn_rnn_out_optional), computed as usual elsewhere.
     x_bounded=True: the caller guarantees |x| <= 1 everywhere (x is the output of a recurrent layer below): the input matrix's
-    weight gradient then needs no pass over x for its column scales (ttrnn_ttlinear_backward_hinted)."""
+    weight gradient then needs no pass over x for its column scales (ttrnn_ttlinear_backward_hinted).
+    lengths: optional per-sample sequence lengths (see device_lengths; include/ttrnn.h TTRNN_HAS_VARLEN): sample b behaves
+    exactly like that sample run alone on x[b, :len_b]; out[b, t] = 0 for t >= len_b; hT / cT are the states after step
+    len_b - 1.  Rows x[b, t >= len_b] never influence a result but must be finite (the weight-gradient kernels multiply them
+    by exact zeros).  Not combined with `stats` (the per-step statistics would include frozen steps) or `prepared` (the
+    call takes the unprepared path).  None: exactly the fixed-length calls."""
     cores_in, cores_hid = list(cores_in), list(cores_hid)
     _require_device(x, h0, c0, bias_in, bias_hid, *(cores_in + cores_hid))
     if x.dim() != 3 or x.shape[2] != spec.input_size:
@@ -762,6 +828,16 @@ def tt_rnn_layer(spec, x, h0, c0, cores_in, bias_in, cores_hid, bias_hid, stats=
     c0 = c0.contiguous().to(x.dtype) if (c0 is not None and spec.cell == "lstm") else None
     spec.recording = torch.is_grad_enabled()
     spec.x_bounded = bool(x_bounded)
+    spec.lengths = None
+    if lengths is not None:
+        if stats is not None:
+            raise ValueError("per-step statistics (log_grads) are not available together with lengths: they would include "
+                             "the frozen steps")
+        lengths = device_lengths(lengths, x.shape[0], x.shape[1], x.device)
+        if not spec.recording:
+            with torch.cuda.device(x.device):
+                return _rnn_forward_nograd(spec, x, h0, c0, cores_in, bias_in, cores_hid, bias_hid, need_out, lengths)
+        spec.lengths = lengths
     if prepared is not None and not spec.recording and stats is None and POISON_ALLOCATIONS is False:
         with torch.cuda.device(x.device):
             return _rnn_forward_prepared(spec, x, h0, c0, bias_in, bias_hid, prepared, need_out)
