@@ -472,9 +472,22 @@ __device__ __forceinline__ F10hScales f10t_scales(const float* __restrict__ hdr,
   }
   return r;
 }
+// ---- round 8: a unit's two pieces on ADJACENT rows of stage 1's A operand (k_lstm_fwd_f10t<.., ADJ = true>) ---------------------
+// Image of one parity: row = 2 j2 + piece, 32 k-values per row.  With the result map col = lane & 15, row = 4 (lane >> 4) + reg,
+// lane (c, q) of tile r2 then holds in registers 0/1 the first- / second-piece sums of j2 = 2 q and in 2/3 those of j2 = 2 q + 1:
+// the fold is an add inside the lane (round 7: the pieces sat eight rows = 32 lanes apart, one v_permlane32_swap per register).
+// Rows are F10T_ROW = 48 halves (96 bytes) apart and the four 16-byte chunks of a row are XORed with row >> 2; by the LDS rules
+// (ds_read_b128: four 16-lane groups, 64 banks; ds_write_b16: two 32-lane halves, 32 banks) the row read and both piece writes
+// of a step are then conflict-free (tests/test_f10t_layout.py counts them; 64-byte rows without the XOR: read 2-way, writes 8-way).
+// Halves from the parity's base to (row, k); a lane's 16-byte fragment read at (row c, k = 8 q) stays 16-byte aligned.
+static constexpr int F10T_ROW = 48;
+__device__ __forceinline__ constexpr int f10t_img_off(int row, int k) {
+  return row * F10T_ROW + 8 * ((k >> 3) ^ ((row >> 2) & 3)) + (k & 7);
+}
 // stage 2's B operand from core 2, built by the recurrent kernel itself: lane (c, q) holds column i2 = c, k = 8 q + j of k-block kb
-// <-> rank index r2 = 2 kb + (j >> 2) + 4 (q >> 1), j2 = 4 (q & 1) + (j & 3)  (the order the folded stage-1 tiles arrive in)
-template <class S>
+// <-> rank index r2 = 2 kb + (j >> 2) + 4 (q >> 1), j2 = 4 (q & 1) + (j & 3)  (the order the folded stage-1 tiles arrive in);
+// ADJ (fold in the lane): r2 = 4 kb + (j >> 1), j2 = 2 q + (j & 1)
+template <class S, bool ADJ = false>
 __device__ __forceinline__ void f10t_load_g2(xh8 (&g2)[2][2], const float* packed, int lane, const float* __restrict__ hdr) {
   using F = F10<S>;
   const int c = lane & 15, q = lane >> 4;
@@ -484,7 +497,7 @@ __device__ __forceinline__ void f10t_load_g2(xh8 (&g2)[2][2], const float* packe
   for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int r2 = 2 * kb + (j >> 2) + 4 * (q >> 1), j2 = 4 * (q & 1) + (j & 3);
+      const int r2 = ADJ ? 4 * kb + (j >> 1) : 2 * kb + (j >> 2) + 4 * (q >> 1), j2 = ADJ ? 2 * q + (j & 1) : 4 * (q & 1) + (j & 3);
       _Float16 p0, p1;
       split2h(W2[j2 * F::M2 + c * F::R2 + r2] * ldexpf(1.f, 12 + e[F10H_EU + c] + e[F10H_EV + r2]), p0, p1);
       g2[kb][0][j] = p0; g2[kb][1][j] = p1;

@@ -1,201 +1,43 @@
-// ttrnn_fast_f10t.hip — the fused-core TT-LSTM forward kernel with cores 0·1 contracted FIRST (gfx950, round 7).
+// ttrnn_fast_f10t.hip — the fused-core TT-LSTM forward kernel with cores 0·1 contracted FIRST (gfx950, rounds 7 and 8).
+// The kernel template is in ttrnn_f10t_kernel.h; this file instantiates its default time loop (ADJ = true, round 8, below),
+// ttrnn_fast_f10t_r7.hip round 7's loop (ADJ = false, option dev2 bit 4096).
 //
 // k_lstm_fwd_f10q keeps the reference's order: core 2 first (S2), then the fused core W10 = cores 1·0 (S10).  In that order every
 // wave needs ALL of C2 for its S10 tile: a 16 KB image in LDS, sixteen ds_read_b128 per wave and a barrier in front of them, every
 // step.  Here the order is the other one (the scales and layouts: ttrnn_f10_dev.h, "cores 0·1 FIRST"):
 //     stage 1   D[(m, r2)][j2] = sum_{k = (j0, j1)} W10[m][k][r2] h[k][j2]        per wave: 16 rows m, one 16x16x32 tile per r2
 //     stage 2   out[m][i2]     = sum_{(r2, j2)} D[m][(r2, j2)] G2[(r2, j2)][i2]    per wave: 16 rows m, K = 64
-// Stage 1 needs only h: 256 values, 1 KB as two fp16 pieces, ONE ds_read_b128 per lane.  h is the A operand (rows 0-7 = first
-// pieces of j2 = row, rows 8-15 = second pieces), W10[., ., r2] of the wave's 16 rows the B operand: the result tile has m on the
-// lane and four consecutive j2 in the registers, first-piece rows in lanes 0-31 and second-piece rows in lanes 32-63.  One
-// v_permlane32_swap per register folds a PAIR of tiles (r2 = p, p + 4) so that every lane holds sixteen live sums — which already
-// ARE stage 2's A operand (row = m, k = 8 q + j), no LDS, no barrier in between.  Per wave and step: 16 + 6 MFMAs (28 before),
-// one LDS read (20 before), one barrier (two before).  Measured on cfg2 (profiles/r7/): 478.5 -> 378.5 us per call.
+// Stage 1 needs only h: 256 values, 1 KB as two fp16 pieces, ONE ds_read_b128 per lane.  h is the A operand, W10[., ., r2] of the
+// wave's 16 rows the B operand: the result tile has m on the lane and h's rows in the registers.  Folded (first-piece sum +
+// second-piece sum) and split again, the eight tiles already ARE stage 2's A operand (row = m, k = 8 q + j), no LDS, no barrier
+// in between.  Per wave and step: 16 + 6 MFMAs (28 before), one LDS read (20 before), one barrier (two before).
+//   Round 7 (ADJ = false): rows 0-7 = first pieces of j2 = row, rows 8-15 = second pieces; a unit's two sums land 32 lanes apart and
+// one v_permlane32_swap per register folds a PAIR of tiles (r2 = p, p + 4).  cfg2 (profiles/r7/): 478.5 -> 378.5 us per call.
+//   Round 8 (ADJ = true, the default): row 2 j2 + piece.  Lane (c, q) of tile r2 holds in registers 0/1 the two sums of j2 = 2 q and
+// in 2/3 those of j2 = 2 q + 1: the fold is two adds in the lane (the same two addends as before: the same bits), one split_pair_h
+// per tile, tile r2 -> dword r2 & 3 of k-block r2 >> 2, i.e. k = 8 q + j <-> r2 = 4 kb + (j >> 1), j2 = 2 q + (j & 1)
+// (f10t_load_g2<S, true> builds core 2's fragment in that order; stage 2 sums in another order than round 7, so the two loops agree
+// to rounding, not bit for bit: tests/test_f10t_loop.py).  The image's rows are 96 bytes apart and a row's four 16-byte chunks are
+// XORed with row >> 2 (f10t_img_off): by the LDS rules the ds_read_b128 (four 16-lane groups, 64 banks) and both ds_write_b16 (two
+// 32-lane halves, 32 banks) are conflict-free (degree 1; tests/test_f10t_layout.py counts it; 64-byte rows: read 2-way, writes
+// 8-way).  The next step's fragment is read right behind the barrier, at the END of the step, so that the pointer bumps and the loop
+// control issue in the read's shadow and not in front of it.  The file is built with -fno-slp-vectorize (csrc/Makefile): with the
+// vectoriser on, every tile's two adds become a v_pk_add_f32 behind three v_mov (24 v_mov per step) and the layout gains nothing.
+// Time loop of the benchmark's instantiation <S, false, true, true, true>, per step: 153 instructions (round 7: 147) — 22 v_mfma,
+// 0 v_permlane32_swap (16), 21 v_add_f32 (5), 16 v_cvt_pk_f16_f32, 16 v_fma_mix_f32, 6 v_fma_f32, 5 v_exp_f32, 5 v_rcp_f32,
+// 3 packed f32 (the accumulators' un-scaling behind the last MFMA; round 7: 13), 7 v_mov, 21 cycles of s_nop pads (round 7: 24), 2 ds_write_b16, 1 ds_read_b128, 1 global store (3 with reserve records), 1 barrier.
+// Measured on cfg2 (profiles/r8/ab_cfg2_f10t_loop.txt): 378.1 -> 317.3 us per call; layout alone (vectoriser on) no gain, layout +
+// flag -8.7 %, + read behind the barrier -15.4 %; the input term x_{t+1} moved behind the read too was 3.7 % SLOWER and is not in.
 // The stage-1 fragments are built in the prologue from the packed cores (f10t_build_w10: the workspace of the shape has no room
 // for a second set), core 2's fragment too; from the workspace only the header's eu / ev are read.
-// Resources (-Rpass-analysis=kernel-resource-usage): 191 ... 196 VGPRs over the instantiations (the prologue's peak; the time loop
-// holds 64 + 16 of fragments), 0 AGPRs, 0 scratch, 2 112 bytes of LDS.
+// Resources (-Rpass-analysis=kernel-resource-usage): 184 ... 192 VGPRs over the instantiations (round 7's loop: 191 ... 196; the
+// prologue's peak; the time loop holds 64 + 16 of fragments), 0 AGPRs, 0 scratch, 3 136 bytes of LDS (round 7's loop: 2 112).
 // Same unit ownership as k_lstm_fwd_f10q (lane (c, q) of wave w: unit (4 w + q) 16 + c, accumulator registers = gates i, f, g, o),
 // same gate phase, input paths, reserve records and stores.
 // Replaces the same reference code as ttrnn_fast_f10.hip: tensorized_rnn/lstm.py:23-32,123-133 + t3nsor/ops.py:78-93.
-#include <hip/hip_runtime.h>
-#include <stdlib.h>
-#include "ttrnn_core.h"
-#include "ttrnn_launch.h"
-#include "ttrnn_opts.h"
-#include "ttrnn_mfma.h"
-#include "ttrnn_split.h"
-#include "ttrnn_f10.h"
-#include "ttrnn_f10_dev.h"
+#include "ttrnn_f10t_kernel.h"
 
 namespace ttrnn {
-
-// fp16 pieces of 2^4 h as stage 1's A operand, [parity][piece][j2][k = 32], + four floats for f10h_h0_expo
-static constexpr size_t F10T_LDS_BYTES = 2 * 2 * 8 * 32 * sizeof(_Float16) + 64;
-
-// H0 / OUT / IN1 / DIAG: as k_lstm_fwd_f10q
-template <class S, bool H0, bool OUT, bool IN1, bool DIAG = false>
-__global__ void __launch_bounds__(256, 2) k_lstm_fwd_f10t(int B, int T, GinSrc gs, const float* __restrict__ h0,
-                                                          const float* __restrict__ c0, const float* __restrict__ packed_hid,
-                                                          const float* __restrict__ hdr,
-                                                          const float* __restrict__ bias_hid, float* __restrict__ out,
-                                                          float* __restrict__ hT, float* __restrict__ cT,
-                                                          float* __restrict__ reserve) {
-  static_assert(f10_ok<S>(), "shape not supported by the fused-core kernel");
-  using F = F10<S>;
-  static_assert(F::MT == 4 && F::ROWS2 == 32 && F::J2 == 8 && F::R2 == 8 && F::I2 == 16 && F::M == 64, "H = 256, r = 8");
-  constexpr int H = F::H;
-  constexpr int PAR = 2 * 8 * 32;                         // fp16 elements per parity of the h image
-
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_t[];
-  _Float16* himg = reinterpret_cast<_Float16*>(smem_t);
-  float* scratch = reinterpret_cast<float*>(himg + 2 * PAR);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  xh8 w10[F::R2][2];                                      // stage 1's B operand: built here (ttrnn_f10_dev.h)
-  const F10hScales fsc = f10t_scales(hdr, f10t_build_w10<S>(w10, packed_hid, hdr, wave, lane), lane);
-  const float hsc = F10T_HSC;
-  const f32x4 psc = fsc.pre, usc = fsc.un;
-  const int c = lane & 15, q = lane >> 4;
-  const size_t b = blockIdx.x;
-
-  xh8 g2[2][2];                                           // [k-block][piece]
-  f10t_load_g2<S>(g2, packed_hid, lane, hdr);
-
-  // the hidden unit of this lane: hid = (4*wave + q)*I2 + c, gates in acc[0..3] = i,f,g,o; gin slots i,g,f,o
-  const float* __restrict__ gin = gs.gin;
-  const float* __restrict__ xs = reinterpret_cast<const float*>(gs.x);
-  constexpr bool in1 = IN1;
-  const int hd = (4 * wave + q) * F::I2 + c;
-  const int hoff = (hd & 7) * 32 + (hd >> 3);             // (j2, k) of this unit in a piece of the image; second piece: + 256
-  float hst = H0 ? h0[b * H + hd] : 0.f;
-  float cst = c0 ? c0[b * H + hd] : 0.f;
-  float h0sc = 1.0f, h0un = 1.0f;
-  if constexpr (H0) {
-    const int e0 = f10h_h0_expo<4>(hst, scratch, wave, lane);
-    h0sc = ldexpf(1.f, -e0); h0un = ldexpf(1.f, e0);
-  }
-  f32x4 bh = f32x4{0.f, 0.f, 0.f, 0.f}, gi = bh, vv = bh, bb = bh;       // slot order i,g,f,o
-  const f32x4 gsc = f32x4{-1.4426950408889634f, 2.8853900817779268f, -1.4426950408889634f, -1.4426950408889634f} *
-                    f32x4{psc[0], psc[2], psc[1], psc[3]};      // slots i,g,f,o <- accumulator rows i,f,g,o
-  XChunk<float> xq;
-  xq.cur = 0.f; xq.nxt = 0.f;
-  if (in1) xq.init(xs, b * T, T, lane);
-  if (bias_hid) bh = f32x4{bias_hid[hd], bias_hid[2 * H + hd], bias_hid[H + hd], bias_hid[3 * H + hd]};
-  if (T > 0) {
-    if (in1) {
-      bb = *reinterpret_cast<const f32x4*>(gin + (H + hd) * 4);
-      vv = (*reinterpret_cast<const f32x4*>(gin + hd * 4) - bb) * gsc;
-      bb = (bb + bh) * gsc;
-    } else {
-      gi = *reinterpret_cast<const f32x4*>(gin + ((b * T) * H + hd) * 4);
-    }
-  }
-  {
-    _Float16 p0, p1;                                       // parity 0 = h_{-1}
-    split2h(hst * (hsc * h0sc), p0, p1);
-    himg[hoff] = p0; himg[256 + hoff] = p1;
-  }
-  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) here, so that no weight-register wait lands inside the loop
-  lds_barrier();
-
-  unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long last_ = 0;
-  if constexpr (DIAG) last_ = stamp();
-  f32x4 us_t = usc * h0un;                  // step 0 runs on 2^-e0 h_0 (f10h_h0_expo); reset to usc / 1 at the end of it
-  float ps_t = h0sc;
-  for (int t = 0; t < T; ++t) {
-    const _Float16* hp = himg + (t & 1) * PAR;            // pieces of h_{t-1}
-    _Float16* hn = himg + ((t + 1) & 1) * PAR;            // pieces of h_t
-    // ---- stage 1: eight tiles (one per r2), two chained MFMAs each: rows 0-7 = h0 (w0 + w1), rows 8-15 = h1 (w0 + w1) -----------
-    const xh8 ha = *reinterpret_cast<const xh8*>(hp + c * 32 + 8 * q);
-    f32x4 d[F::R2];
-#pragma unroll
-    for (int r = 0; r < F::R2; ++r) d[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha, w10[r][0], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < F::R2; ++r) d[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ha, w10[r][1], d[r], 0, 0, 0);
-    if constexpr (DIAG) {
-#pragma unroll
-      for (int r = 0; r < F::R2; ++r) asm volatile("" : "+v"(d[r]));
-    }
-    TT_STAMP(0)
-    // ---- fold tile pairs (p, p + 4): lanes 0-31 keep r2 = p, lanes 32-63 r2 = p + 4; then the two pieces of every sum ----------
-    unsigned a0[2][4], a1[2][4];                           // [k-block][dword]: stage 2's A operand, k = 8 q + j
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      f32x4 s;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(d[p][j]), __float_as_uint(d[p + 4][j]), false, false);
-        s[j] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-      }
-      split_pair_h(s[0], s[1], a0[p >> 1][2 * (p & 1)], a1[p >> 1][2 * (p & 1)]);
-      split_pair_h(s[2], s[3], a0[p >> 1][2 * (p & 1) + 1], a1[p >> 1][2 * (p & 1) + 1]);
-    }
-    if constexpr (DIAG) {
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(a0[kb][j]), "+v"(a1[kb][j]));
-    }
-    TT_STAMP(1)
-    const size_t bt = b * T + t;
-    // ---- stage 2: d0 g0 into the accumulator that carries the input term, d0 g1 + d1 g0 into its own; gates + state ------------
-    f32x4 acc;
-    {
-      // (W_in x_t + b_in + b_hid) * scale, slots i,g,f,o -> accumulator rows i,f,g,o
-      f32x4 pre = in1 ? bb + xq.at(t) * vv : (gi + bh) * gsc;
-      if constexpr (H0) pre = pre * ps_t;
-      f32x4 acc_lo = f32x4{0.f, 0.f, 0.f, 0.f}, acc_hi = f32x4{pre[0], pre[2], pre[1], pre[3]};
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        const xh8 d0 = __builtin_bit_cast(xh8, u32x4{a0[kb][0], a0[kb][1], a0[kb][2], a0[kb][3]});
-        const xh8 d1 = __builtin_bit_cast(xh8, u32x4{a1[kb][0], a1[kb][1], a1[kb][2], a1[kb][3]});
-        acc_lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(d0, g2[kb][1], acc_lo, 0, 0, 0);
-        acc_lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(d1, g2[kb][0], acc_lo, 0, 0, 0);
-        acc_hi = __builtin_amdgcn_mfma_f32_16x16x32_f16(d0, g2[kb][0], acc_hi, 0, 0, 0);
-      }
-      const f32x4 un = H0 ? us_t : usc;
-      acc = acc_hi * un + acc_lo * un;                    // 2^-S per row and column (2^(e0-S) at step 0 of a given h_0), exact
-      if constexpr (DIAG) asm volatile("" : "+v"(acc));
-    }
-    TT_STAMP(2)
-    const float ig = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[0]));                // lstm.py:26
-    const float fg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[1]));                // lstm.py:27
-    const float gg = 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[2]));  // lstm.py:28
-    const float og = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[3]));                // lstm.py:29
-    const float cy = fg * cst + ig * gg;                    // lstm.py:31
-    const float hy = og * ftanh(cy);                        // lstm.py:32
-    cst = cy;
-    hst = hy;
-    {
-      _Float16 p0, p1;
-      split2h(hy * hsc, p0, p1);
-      hn[hoff] = p0; hn[256 + hoff] = p1;
-    }
-    if constexpr (OUT) out[bt * H + hd] = hy;               // outputs[:, t, :] (lstm.py:133): 256 contiguous bytes per wave
-    if (reserve) {
-      *reinterpret_cast<f32x4*>(reserve + res_gate(bt, H, hd)) = f32x4{ig, gg, fg, og};
-      reserve[res_cell((size_t)B * T, bt, H, hd)] = cy;
-    }
-    if (!in1 && t + 1 < T) gi = *reinterpret_cast<const f32x4*>(gin + ((bt + 1) * H + hd) * 4);
-    if (in1) xq.advance(xs, b * T, T, t, lane);
-    us_t = usc; ps_t = 1.0f;
-    TT_STAMP(3)
-    lds_barrier();                                          // h_t published; the parity read in this step is free for h_{t+1}
-    TT_STAMP(4)
-  }
-  if (hT) hT[b * H + hd] = hst;
-  if (cT) cT[b * H + hd] = cst;
-  if constexpr (DIAG) {
-    if (lane == 0 && reserve && b < 8) {
-      unsigned long long* dst = reinterpret_cast<unsigned long long*>(reserve) + (b * 8 + wave) * 8;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) dst[i] = seg[i];
-    }
-  }
-}
 
 // Default for cfg2's shape in split mode while every sample has a CU of its own (measured: profiles/r7/ab_cfg2_forward.txt);
 // option dev2 bit 2048 keeps k_lstm_fwd_f10q.  More samples than CUs (two workgroups per CU) stay on k_lstm_fwd_f10q: not measured.
@@ -204,22 +46,15 @@ bool f10t_available(const RnnShape& rs) {
   return shape_matches<ShpH256R8L>(rs.hid_s) && rs.B <= device_cu_count();
 }
 
-// ws: the scale header of k_f10h_scale / the fused set-up launch (eu, ev); the old-order fragments behind it are not read
+// ws: the scale header of k_f10h_scale / the fused set-up launch (eu, ev); the old-order fragments behind it are not read.
+// Option dev2 bit 4096: round 7's time loop (fold across the wave's halves; ttrnn_fast_f10t_r7.hip) instead of the fold in the lane (A/B).
 int launch_rnn_fwd_f10_t(const RnnShape& rs, GinSrc gin, const void* h0, const void* c0, const float* packed_hid,
                          const void* ws, const float* bias_hid, void* out, void* hT, void* cT, float* reserve,
                          hipStream_t stream) {
   using S = ShpH256R8L;
   if (!shape_matches<S>(rs.hid_s)) return TTRNN_ERR_UNSUPPORTED;
-  const float* hdr = reinterpret_cast<const float*>(ws);
-  auto kern = gin.in1 ? (out ? (h0 ? k_lstm_fwd_f10t<S, true, true, true> : k_lstm_fwd_f10t<S, false, true, true>)
-                             : (h0 ? k_lstm_fwd_f10t<S, true, false, true> : k_lstm_fwd_f10t<S, false, false, true>))
-                      : (out ? (h0 ? k_lstm_fwd_f10t<S, true, true, false> : k_lstm_fwd_f10t<S, false, true, false>)
-                             : (h0 ? k_lstm_fwd_f10t<S, true, false, false> : k_lstm_fwd_f10t<S, false, false, false>));
-  if (opt(OPT_DIAG) && reserve && out && !h0)      // stamped build (diagnostics)
-    kern = gin.in1 ? k_lstm_fwd_f10t<S, false, true, true, true> : k_lstm_fwd_f10t<S, false, true, false, true>;
-  hipLaunchKernelGGL(kern, dim3(rs.B), dim3(256), F10T_LDS_BYTES, stream, rs.B, rs.T, gin, (const float*)h0,
-                     (const float*)c0, packed_hid, hdr, bias_hid, (float*)out, (float*)hT, (float*)cT, reserve);
-  return hipGetLastError() == hipSuccess ? TTRNN_OK : TTRNN_ERR_LAUNCH;
+  if (opt(OPT_DEV2) & 4096) return launch_rnn_fwd_f10_t_r7(rs, gin, h0, c0, packed_hid, ws, bias_hid, out, hT, cT, reserve, stream);
+  return launch_f10t<S, true>(rs, gin, h0, c0, packed_hid, reinterpret_cast<const float*>(ws), bias_hid, out, hT, cT, reserve, stream);
 }
 
 }  // namespace ttrnn

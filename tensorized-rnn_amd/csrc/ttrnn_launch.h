@@ -195,6 +195,9 @@ bool f10_fwd_takes_f10t(const RnnShape& rs);      // launch_rnn_fwd_f10's routin
 int launch_rnn_fwd_f10_t(const RnnShape& rs, GinSrc gin, const void* h0, const void* c0, const float* packed_hid,
                          const void* ws, const float* bias_hid, void* out, void* hT, void* cT, float* reserve,
                          hipStream_t stream);
+int launch_rnn_fwd_f10_t_r7(const RnnShape& rs, GinSrc gin, const void* h0, const void* c0, const float* packed_hid,
+                            const void* ws, const float* bias_hid, void* out, void* hT, void* cT, float* reserve,
+                            hipStream_t stream);      // round 7's time loop (option dev2 bit 4096): ttrnn_fast_f10t_r7.hip
 int launch_rnn_fwd_f10_q(const RnnShape& rs, GinSrc gin, const void* h0, const void* c0, const float* packed_hid,
                            const void* wfrag, const float* bias_hid, void* out, void* hT, void* cT, float* reserve,
                            hipStream_t stream);

@@ -49,6 +49,7 @@ enum OptId {
                          //                         512: naive per-gate sets of H = 256 on the tier's reverse-time kernel (instead of k_rnn_bwd_f10n),
                          //                         1024: the four-barrier fused-core LSTM reverse kernel instead of its wave-local form (k_lstm_bwd_f10h<.., WL>),
                          //                         2048: k_lstm_fwd_f10q (core 2 first, S10 image in LDS) for the calls k_lstm_fwd_f10t (cores 0·1 first, register hand-off) would take,
+                         //                         4096: round 7's time loop of k_lstm_fwd_f10t (a unit's two fp16 pieces eight MFMA rows apart, fold by v_permlane32_swap; ttrnn_fast_f10t_r7.hip) instead of the default loop (pieces on adjacent rows, fold in the lane),
                          //                         (-DTTRNN_ABLATIONS builds only, tools/c2w_bench.py: bits 16 and up are the chain kernels' ablation switches)
   OPT_COUNT
 };
