@@ -137,8 +137,20 @@ int ttrnn_get_fp32_math(void);
  *   "bf16_fp32_mfma",
  *   "big_merge" (0..2), "big_no_gemm", "big_no_pair", "no_bigb", "bigw_slices", "f10_nb1", "dense_fp32", "f10_nb2",
  *   "gemm_pieces" (0 | 2 | 3), "big_fp32_mfma", "pair_fault" (tests only: exercises the pair kernels' time-out path),
- *   "no_gemm3", "dev" (0..1073741823: developer bit mask, A/B route switches between kernels that compute the same result;
- *   csrc/ttrnn_opts.h lists the bits).
+ *   "no_gemm3";
+ *   the A/B route switches between two kernels that compute the same result (csrc/ttrnn_opts.h says what each selects):
+ *   "gemm3_pingpong", "f10gq_bf16", "gru_eight_wave", "gemm3_wg_per_tile", "f10bl_always", "gru_fwd_on_tier", "f10s",
+ *   "no_proj3", "g2_bwd_head_streamed", "g2_four_wave_streamed", "h512_fwd_on_tier", "h512_bwd_on_tier", "f10bl_never",
+ *   "no_fused_setup", "f10p", "head_split_epilogue", "g2_pair_never", "g2_pair_always", "g2_bwd_four_wave",
+ *   "g2_bwd_t2_general", "no_proj4", "g2_dense_from_merged", "naive_fwd_on_tier", "gru_r16_bwd_stagewise", "g2_no_cin",
+ *   "dense_one_round_rule", "g2_bwd_one_tile", "no_chain_wgrad", "chain_wgrad_hid_only", "c2_runtime_plan",
+ *   "chain_wgrad_large", "enc_fwd_on_tier", "enc_bwd_on_tier", "c2r_off", "gru_r16_bwd_on_tier", "gru_h512_bwd_on_tier",
+ *   "naive_bwd_on_tier", "f10bh_no_wl", "f10t_off", "f10t_r7_loop";
+ *   "dev", "dev2" (0..1073741823 each): the two words whose bits the route switches used to be, kept for old numeric
+ *   command lines and for the result-destroying ablations of -DTTRNN_ABLATIONS builds.  Setting a word sets every route
+ *   switch to its bit of the word (csrc/ttrnn_opts.h has the masks), and reading it shows the switches that are on:
+ *   either spelling sees what the other wrote.  Where TTRNN_DEV / TTRNN_DEV2 and a switch's own variable are both in the
+ *   environment, the named variable wins.
  * Workspace sizes must be queried under the same options the launch will run with.
  * Returns TTRNN_OK, or TTRNN_ERR_UNSUPPORTED for an unknown name / value out of range. */
 int ttrnn_set_option(const char* name, int value);
@@ -304,7 +316,7 @@ int ttrnn_rnn_forward_route(const ttrnn_rnn_desc* desc);   /* TTRNN_ROUTE_* or a
  * bad descriptor. */
 int ttrnn_rnn_forward_samples_per_workgroup(const ttrnn_rnn_desc* desc);
 /* 1 when the recurrent forward kernel of this descriptor contracts cores 0·1 of the hidden matrix first (k_lstm_fwd_f10t: TT-LSTM
- * H = 256, d = 3, r = 8, split math mode, no more samples than CUs; option dev2 bit 2048 keeps k_lstm_fwd_f10q), else 0.  Pure
+ * H = 256, d = 3, r = 8, split math mode, no more samples than CUs; option f10t_off keeps k_lstm_fwd_f10q), else 0.  Pure
  * host logic; a negative ttrnn_status on a bad descriptor. */
 int ttrnn_rnn_forward_cores01_first(const ttrnn_rnn_desc* desc);
 
@@ -332,8 +344,8 @@ int ttrnn_rnn_forward_cores01_first(const ttrnn_rnn_desc* desc);
  *       d_out and d_hT may each be NULL = zeros; d_out_seeded may not alias d_out)
  *   ttrnn_rnn_backward_ex(..., d_out = d_out_seeded, d_hT = NULL, d_cT as given, ...)            (GRU too: one rule)
  *   ttrnn_rnn_wgrad / ttrnn_ttlinear_backward_hinted                                              unchanged.
- * Kernels.  ttrnn_rnn_forward_varlen_route reports the family that takes the call under the current options (dev2, force_generic,
- * fp32_math as ttrnn_rnn_forward_route): TTRNN_ROUTE_FUSED_CORE for the encoder-shape kernels (H = 768, 40 inputs), otherwise
+ * Kernels.  ttrnn_rnn_forward_varlen_route reports the family that takes the call under the current options
+ * (enc_fwd_on_tier, force_generic, fp32_math as ttrnn_rnn_forward_route): TTRNN_ROUTE_FUSED_CORE for the encoder-shape kernels (H = 768, 40 inputs), otherwise
  * TTRNN_ROUTE_RUNTIME_MFMA (always one sample per workgroup) or TTRNN_ROUTE_VALU.  The other shape-specialised forward kernels
  * do not take lengths; their shapes run the runtime tier.  Each workgroup's time loop ends at its own sample's length.
  * Conventions as everywhere: no allocation, no synchronisation, capture-safe (lengths are read on the device at replay time);
@@ -413,7 +425,7 @@ int ttrnn_rnn_backward_ex(const ttrnn_rnn_desc* desc, const void* out, const voi
  *   x_colmax [in] / h_colmax [H] / dy_colmax_in / dy_colmax_hid [G*H]: optional UPPER BOUNDS (fp32, as ttrnn_lin_hints) of the
  *                      operands' magnitudes — what missing ones cost is a pass over the operand.
  * ttrnn_rnn_wgrad_workspace: bytes, or 0 = this descriptor (or `mats`) is not taken by the chain kernel under the current options
- * (fp32 storage and split fp32 math only; option dev2 bit 0 switches the route off) — call ttrnn_ttlinear_backward_hinted then.
+ * (fp32 storage and split fp32 math only; option no_chain_wgrad switches the route off) — call ttrnn_ttlinear_backward_hinted then.
  * Sums over the rows are added in a fixed order: the gradients are repeatable bit for bit. */
 typedef struct ttrnn_wgrad_args {
   const void* x;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
+#include <ctype.h>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -14,27 +15,56 @@
 
 using namespace ttrnn;
 
-// ---- options: one table, filled once from TTRNN_* environment variables, atomics afterwards (ttrnn_opts.h) ---------
+// ---- options: generated from the one table of ttrnn_opts.h; environment at first use, relaxed atomics afterwards ----------------
 namespace ttrnn {
 namespace {
+enum OptKind { BOOL, R02, S023, MATH, WORD };
+struct OptRow { const char* name; OptKind kind; int def; OptId word; int mask; };
+const OptRow kOpts[OPT_COUNT] = {
+#define TTRNN_OPT_ROW(id, name, kind, def, word, mask, desc) {name, kind, def, OPT_##word, mask},
+    TTRNN_OPTIONS(TTRNN_OPT_ROW)
+#undef TTRNN_OPT_ROW
+};
+bool opt_valid(OptKind k, int v) {
+  switch (k) {
+    case R02: return v >= 0 && v <= 2;
+    case S023: return v == 0 || v == 2 || v == 3;
+    case MATH: return v == TTRNN_MATH_EXACT || v == TTRNN_MATH_SPLIT;
+    case WORD: return v >= 0 && v <= 0x3FFFFFFF;
+    default: return v == 0 || v == 1;
+  }
+}
+int opt_parse(const OptRow& r, const char* e) {      // the value of an environment variable that is set
+  switch (r.kind) {
+    case R02: return e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : r.def;
+    case S023: return e[0] == '2' || e[0] == '3' ? e[0] - '0' : r.def;
+    case MATH: return e[0] == 'e' || e[0] == '0' ? TTRNN_MATH_EXACT : TTRNN_MATH_SPLIT;
+    case WORD: return atoi(e) & 0x3FFFFFFF;
+    default: return e[0] == '1';
+  }
+}
 struct OptTable {
   std::atomic<int> v[OPT_COUNT];
+  // a word carries its switches with it, and a switch shows in its word: either spelling reads what the other wrote
+  void store(int i, int value) {
+    const OptRow& r = kOpts[i];
+    v[i].store(value, std::memory_order_relaxed);
+    if (r.kind == WORD) {
+      for (int j = 0; j < OPT_COUNT; ++j)
+        if (kOpts[j].word == i) v[j].store((value & kOpts[j].mask) != 0, std::memory_order_relaxed);
+    } else if (r.word != OPT_NONE) {
+      if (value) v[r.word].fetch_or(r.mask, std::memory_order_relaxed);
+      else v[r.word].fetch_and(~r.mask, std::memory_order_relaxed);
+    }
+  }
   OptTable() {
-    static const char* const env[OPT_COUNT] = {
-        "TTRNN_FP32_MATH", "TTRNN_FORCE_GENERIC", "TTRNN_NO_GEMM", "TTRNN_NO_IN1", "TTRNN_NO_F10", "TTRNN_NO_G2",
-        "TTRNN_FORCE_G2",
-        "TTRNN_DIAG", "TTRNN_BF16_FP32_MFMA", "TTRNN_BIG_MERGE", "TTRNN_BIG_NO_GEMM", "TTRNN_BIG_NO_PAIR",
-        "TTRNN_NO_BIGB", "TTRNN_BIGW_SLICES", "TTRNN_F10_NB1", "TTRNN_DENSE_FP32", "TTRNN_F10_NB2", "TTRNN_GEMM_PIECES",
-        "TTRNN_BIG_FP32_MFMA", "TTRNN_PAIR_FAULT", "TTRNN_NO_GEMM3", "TTRNN_DEV", "TTRNN_DEV2"};
-    for (int i = 0; i < OPT_COUNT; ++i) {
-      const char* e = getenv(env[i]);
-      int val = 0;
-      if (i == OPT_FP32_MATH) val = (e && (e[0] == 'e' || e[0] == '0')) ? TTRNN_MATH_EXACT : TTRNN_MATH_SPLIT;
-      else if (i == OPT_BIG_MERGE) val = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2;
-      else if (i == OPT_GEMM_PIECES) val = (e && (e[0] == '2' || e[0] == '3')) ? e[0] - '0' : 0;
-      else if (i == OPT_DEV || i == OPT_DEV2) val = e ? (atoi(e) & 0x3FFFFFFF) : 0;
-      else val = (e && e[0] == '1') ? 1 : 0;
-      v[i].store(val, std::memory_order_relaxed);
+    for (int i = 0; i < OPT_COUNT; ++i) v[i].store(kOpts[i].def, std::memory_order_relaxed);
+    for (int i = 0; i < OPT_COUNT; ++i) {      // in table order: the words first, so that a named variable wins over TTRNN_DEV / TTRNN_DEV2
+      char env[64] = "TTRNN_";
+      size_t n = strlen(env);
+      for (const char* c = kOpts[i].name; *c && n + 1 < sizeof env; ++c) env[n++] = (char)toupper((unsigned char)*c);
+      env[n] = 0;
+      if (const char* e = getenv(env)) store(i, opt_parse(kOpts[i], e));
     }
   }
 };
@@ -42,28 +72,18 @@ OptTable& table() {
   static OptTable t;      // thread-safe initialisation (C++11 magic static)
   return t;
 }
-const char* const kOptNames[OPT_COUNT] = {
-    "fp32_math", "force_generic", "no_gemm", "no_in1", "no_f10", "no_g2", "force_g2", "diag", "bf16_fp32_mfma", "big_merge",
-    "big_no_gemm", "big_no_pair", "no_bigb", "bigw_slices", "f10_nb1", "dense_fp32", "f10_nb2", "gemm_pieces", "big_fp32_mfma",
-    "pair_fault", "no_gemm3", "dev", "dev2"};
-}  // namespace
-int opt(OptId id) { return table().v[id].load(std::memory_order_relaxed); }
-const char* opt_name(OptId id) { return kOptNames[id]; }
-static int opt_find(const char* name) {
-  if (!name) return -1;
-  for (int i = 0; i < OPT_COUNT; ++i)
-    if (strcmp(name, kOptNames[i]) == 0) return i;
+int opt_find(const char* name) {
+  for (int i = 0; name && i < OPT_COUNT; ++i)
+    if (strcmp(name, kOpts[i].name) == 0) return i;
   return -1;
 }
+}  // namespace
+int opt(OptId id) { return table().v[id].load(std::memory_order_relaxed); }
+const char* opt_name(OptId id) { return kOpts[id].name; }
 int opt_set(const char* name, int value) {
   const int i = opt_find(name);
-  if (i < 0) return -1;
-  if (i == OPT_FP32_MATH && value != TTRNN_MATH_EXACT && value != TTRNN_MATH_SPLIT) return -1;
-  if (i == OPT_BIG_MERGE && (value < 0 || value > 2)) return -1;
-  if (i == OPT_GEMM_PIECES && value != 0 && value != 2 && value != 3) return -1;
-  if ((i == OPT_DEV || i == OPT_DEV2) && (value < 0 || value > 0x3FFFFFFF)) return -1;
-  if (i != OPT_FP32_MATH && i != OPT_BIG_MERGE && i != OPT_GEMM_PIECES && i != OPT_DEV && i != OPT_DEV2 && value != 0 && value != 1) return -1;
-  table().v[i].store(value, std::memory_order_relaxed);
+  if (i < 0 || !opt_valid(kOpts[i].kind, value)) return -1;
+  table().store(i, value);
   return 0;
 }
 int opt_get(const char* name, int* value) {
@@ -1063,13 +1083,13 @@ int ttrnn_rnn_backward_ex(const ttrnn_rnn_desc* desc, const void* out, const voi
 // which matrices of `mats` the chain kernel takes in ONE launch for this descriptor (0: none)
 static int wgrad_chain_mats(const RnnShape& rs, int dtype, int mats, const TtShape* shapes[2], int* hid_slot) {
   *hid_slot = -1;
-  if (dtype != TTRNN_F32 || fp32_math() != TTRNN_MATH_SPLIT || force_generic() || no_gemm() || (opt(OPT_DEV2) & 1)) return 0;
+  if (dtype != TTRNN_F32 || fp32_math() != TTRNN_MATH_SPLIT || force_generic() || no_gemm() || opt(OPT_NO_CHAIN_WGRAD)) return 0;
   if (rs.hid_blocks > 1) return 0;                 // (joint matrices of naive sets: their block structure is not exploited here)
   if (!(mats & 2) || !c2w_prefers_chain(rs.hid_s)) return 0;      // the hidden matrix decides
   int n = 0;
-  const bool small = !(opt(OPT_DEV2) & 8);      // (dev2 bit 3: the large kernel variant too — measured slower than the dense gradient)
+  const bool small = !opt(OPT_CHAIN_WGRAD_LARGE);      // (option chain_wgrad_large: the large kernel variant too — measured slower than the dense gradient)
   // the input matrix rides along where it shares the gate gradients (LSTM) and the kernel takes the pair
-  if ((mats & 1) && rs.cell == TTRNN_LSTM && rs.in >= 4 && !(opt(OPT_DEV2) & 2)) {
+  if ((mats & 1) && rs.cell == TTRNN_LSTM && rs.in >= 4 && !opt(OPT_CHAIN_WGRAD_HID_ONLY)) {
     const TtShape* both[2] = {&rs.in_s, &rs.hid_s};
     if (c2w_workspace_bytes(both, 2, small) > 0) { shapes[0] = &rs.in_s; shapes[1] = &rs.hid_s; *hid_slot = 1; return 3; }
   }

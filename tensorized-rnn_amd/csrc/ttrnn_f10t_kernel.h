@@ -1,6 +1,6 @@
 // ttrnn_f10t_kernel.h — k_lstm_fwd_f10t (the fused-core TT-LSTM forward with cores 0·1 contracted first) and its launcher, for the
 // two translation units that instantiate it: ttrnn_fast_f10t.hip (ADJ = true, the default loop; built with -fno-slp-vectorize) and
-// ttrnn_fast_f10t_r7.hip (ADJ = false, round 7's loop behind option dev2 bit 4096; built with the plain flags, so that its code is
+// ttrnn_fast_f10t_r7.hip (ADJ = false, round 7's loop behind option f10t_r7_loop; built with the plain flags, so that its code is
 // the code it was measured with).  Description, layouts, instruction counts and resources: ttrnn_fast_f10t.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,7 +21,7 @@ template <bool ADJ>
 static constexpr size_t F10T_LDS_BYTES = 2 * (ADJ ? 16 * F10T_ROW : 2 * 8 * 32) * sizeof(_Float16) + 64;
 
 // H0 / OUT / IN1 / DIAG: as k_lstm_fwd_f10q.  ADJ: a unit's two pieces on adjacent rows of stage 1's A operand, fold in the lane
-// (round 8); false = round 7's loop (pieces eight rows apart, fold across the wave's halves), option dev2 bit 4096
+// (round 8); false = round 7's loop (pieces eight rows apart, fold across the wave's halves), option f10t_r7_loop
 template <class S, bool H0, bool OUT, bool IN1, bool ADJ, bool DIAG = false>
 __global__ void __launch_bounds__(256, 2) k_lstm_fwd_f10t(int B, int T, GinSrc gs, const float* __restrict__ h0,
                                                           const float* __restrict__ c0, const float* __restrict__ packed_hid,

@@ -900,12 +900,12 @@ int c2_launch_main(const C2Args& a, hipStream_t stream) {
   constexpr C2Plan spk = c2_const_plan<SP>();
   constexpr int SP4 = NMAT == 2 ? 3 : 4, SD2 = NMAT == 2 ? 5 : 6, SD4 = NMAT == 2 ? 7 : 8;
   constexpr C2Plan spk4 = c2_const_plan<SP4>(), sd2 = c2_const_plan<SD2>(), sd4 = c2_const_plan<SD4>();
-  const bool ct = !(opt(OPT_DEV2) & 4);
+  const bool ct = !opt(OPT_C2_RUNTIME_PLAN);
   if (pl.big && ct && c2_same_kernel_plan(pl, spk4)) kf = k_c2w<SP4, NMAT, C2_NW, 8, 2, 2, 8, 2>;
   else if (pl.big && ct && c2_same_kernel_plan(pl, sd2)) kf = k_c2w<SD2, NMAT, C2_NW, 8, 2, 2, 8, 2>;
   else if (pl.big && ct && c2_same_kernel_plan(pl, sd4)) kf = k_c2w<SD4, NMAT, C2_NW, 8, 2, 2, 8, 2>;
   else if (pl.big) kf = k_c2w<0, NMAT, C2_NW, 8, 2, 2, 8, 2>;
-  else if (c2_same_kernel_plan(pl, spk) && !(opt(OPT_DEV2) & 4)) kf = k_c2w<SP, NMAT, C2_NW, 4, 1, 1, 4, 1>;      // (dev2 bit 2: the run-time-plan kernel, A/B)
+  else if (c2_same_kernel_plan(pl, spk) && !opt(OPT_C2_RUNTIME_PLAN)) kf = k_c2w<SP, NMAT, C2_NW, 4, 1, 1, 4, 1>;      // (option c2_runtime_plan: the run-time-plan kernel, A/B)
   else kf = k_c2w<0, NMAT, C2_NW, 4, 1, 1, 4, 1>;
   fn = reinterpret_cast<const void*>(kf);
   if (ensure_dynamic_lds(fn, pl.lds) != TTRNN_OK) return TTRNN_ERR_LAUNCH;
@@ -1022,7 +1022,7 @@ int c2r_launch(const TtShape* const* shapes, int64_t n_rows, const float* const*
   C2RRed ra{};
   ka.dy = dy; ka.n_rows = (long)n_rows;
 #ifdef TTRNN_ABLATIONS
-  ka.abl = opt(OPT_DEV2) >> 16;
+  ka.abl = opt(OPT_DEV2) >> DEV2_ABLATIONS_SHIFT;
   ka.diag = (unsigned long long*)(ws + w.cmax + 64);
 #endif
   ka.part = (float*)(ws + w.part);
@@ -1103,9 +1103,9 @@ struct C2RLaunchVisit {
     return true;
   }
 };
-// bytes of the hand-off kernel's workspace; 0 = it does not take the call (option dev2 bit 6: never — the A/B against k_c2w)
+// bytes of the hand-off kernel's workspace; 0 = it does not take the call (option c2r_off: never — the A/B against k_c2w)
 size_t c2r_workspace_bytes(const TtShape* const* shapes, int nmat) {
-  if (opt(OPT_DEV2) & 64) return 0;
+  if (opt(OPT_C2R_OFF)) return 0;
   size_t b = 0;
   c2r_each(C2RWsVisit{shapes, nmat, &b});
   return b;
@@ -1129,7 +1129,7 @@ bool c2w_prefers_chain(const TtShape& s) {
 
 // small_only: only plans of the small kernel variant count.  That is what the router offers: the large variant (P > 128 rows of
 // Gt: rank 4 at H = 768, the d = 4 shapes) spills its run-time plan and LOSES to the dense gradient (H = 768, d = 2, r = 4 at
-// the speaker encoder's size: 4.9 ms against 1.8) — it stays reachable for tests through option dev2 bit 3.
+// the speaker encoder's size: 4.9 ms against 1.8) — it stays reachable for tests through option chain_wgrad_large.
 size_t c2w_workspace_bytes(const TtShape* const* shapes, int nmat, bool small_only) {
   const size_t rb = c2r_workspace_bytes(shapes, nmat);
   if (rb) return rb;
@@ -1180,7 +1180,7 @@ int launch_c2w(const TtShape* const* shapes, int nmat, int64_t n_rows, const flo
   C2RedArgs ra{};
   ka.pl = pl; ka.dy = dy; ka.n_rows = (long)n_rows;
 #ifdef TTRNN_ABLATIONS
-  ka.abl = opt(OPT_DEV2) >> 16;
+  ka.abl = opt(OPT_DEV2) >> DEV2_ABLATIONS_SHIFT;
   ka.diag = (unsigned long long*)(ws + pl.w_cmax + 64);
 #endif
   ka.bpart = (d_bias0 || d_bias1) ? (float*)(ws + pl.w_bpart) : nullptr;

@@ -652,7 +652,7 @@ __global__ void __launch_bounds__(FAST_NT) k_gru_fwd_f10(int B, int T, GinSrc gs
   if (own && hT) st(hT, b * H + hid, hst);
 }
 
-// Four-wave variant with S2 INSIDE the gate waves (the default; option `dev` bit 5 selects the eight-wave kernel above for
+// Four-wave variant with S2 INSIDE the gate waves (the default; option gru_eight_wave selects the eight-wave kernel above for
 // A/B — the two agree to one bf16 ulp of the stored C2 / h: the MFMA sums the same eight products with k in other slots):
 // wave w owns hidden units
 // 64w .. 64w+63 = chain rows 8w .. 8w+7, so the S2 operand of those rows — eight consecutive units per row — lives in eight
@@ -800,7 +800,7 @@ static int launch_f10g(const RnnShape& rs, GinSrc gin, const void* h0, const flo
   if (phase != TTRNN_PHASE_RUN)
     hipLaunchKernelGGL((k_f10g_prep<S>), dim3(4 * F10<S>::NM), dim3(64), 0, stream, packed_hid, wfrag);
   if (phase == TTRNN_PHASE_PREPARE) return hipGetLastError() == hipSuccess ? TTRNN_OK : TTRNN_ERR_LAUNCH;
-  if (!(opt(OPT_DEV) & 32)) {    // default: four waves, S2 inside the gate waves (dev bit 5: the eight-wave kernel, A/B)
+  if (!opt(OPT_GRU_EIGHT_WAVE)) {    // default: four waves, S2 inside the gate waves (option gru_eight_wave: the eight-wave kernel, A/B)
     auto kern = gin.in1 ? (out ? k_gru_fwd_f10v<S, true, true> : k_gru_fwd_f10v<S, false, true>)
                         : (out ? k_gru_fwd_f10v<S, true, false> : k_gru_fwd_f10v<S, false, false>);
     hipLaunchKernelGGL(kern, dim3(rs.B), dim3(256), 0, stream, rs.B, rs.T, gin, (const bf16_t*)h0, packed_hid,
@@ -843,7 +843,7 @@ static int launch_f10(const RnnShape& rs, GinSrc gin, const void* h0, const void
   if (!dg && !opt(OPT_F10_NB1)) {
     if (rs.B > cus && opt(OPT_F10_NB2))
       return launch_rnn_fwd_f10_nb2(rs, gin, h0, c0, packed_hid, ws, bh, out, hT, cT, reserve, stream);
-    // one barrier per step, S2 inside the gate waves (ttrnn_fast_f10s.hip, round 5): measured slower, dev bit 512 selects it (A/B)
+    // one barrier per step, S2 inside the gate waves (ttrnn_fast_f10s.hip, round 5): measured slower, option f10s selects it (A/B)
     if (KS == 1 && f10s_available(rs, h0 != nullptr))
       return launch_rnn_fwd_f10_s(rs, gin, h0, c0, packed_hid, ws, bh, out, hT, cT, reserve, stream);
     // cores 0·1 first, stage hand-off in registers (ttrnn_fast_f10t.hip, round 7): r = 8 while every sample has its own CU
@@ -889,9 +889,9 @@ int launch_rnn_fwd_f10(const RnnShape& rs, GinSrc gin, const void* h0, const voi
                        const void* bias_hid, void* out, void* hT, void* cT, float* reserve, void* ws,
                        hipStream_t stream, int phase) {
   if (rs.cell == TTRNN_GRU) {
-    // dev bit 2 (A/B): four waves with the gates in the lanes that hold the sums (ttrnn_fast_f10gq.hip) — built for VERDICT r2
+    // option f10gq_bf16 (A/B): four waves with the gates in the lanes that hold the sums (ttrnn_fast_f10gq.hip) — built for VERDICT r2
     // item 4 and measured SLOWER than the eight-wave kernel below (0.678 against 0.570 ms on cfg3), so it is not the default
-    if ((opt(OPT_DEV) & 4) && f10gq_available(rs, TTRNN_BF16))
+    if (opt(OPT_F10GQ_BF16) && f10gq_available(rs, TTRNN_BF16))
       return launch_gru_fwd_f10gq(rs, gin, h0, packed_hid, bias_hid, out, hT, reserve, ws, stream, phase);
     if (shape_matches<ShpH256R8G>(rs.hid_s))
       return launch_f10g<ShpH256R8G>(rs, gin, h0, packed_hid, bias_hid, out, hT, reserve, ws, stream, phase);
@@ -917,7 +917,7 @@ size_t f10_h512_workspace_bytes() {
   return f10_wfrag_bytes<ShpH512R8L>() > f10_wfrag_bytes<ShpH384R8L>() ? f10_wfrag_bytes<ShpH512R8L>() : f10_wfrag_bytes<ShpH384R8L>();
 }
 bool f10_h512_fwd_available(const RnnShape& rs, int dtype) {
-  return !opt(OPT_NO_F10) && !(opt(OPT_DEV) & 8192) && rs.B >= 1 && rs.T >= 1 && dtype == TTRNN_F32 && rs.cell == TTRNN_LSTM &&
+  return !opt(OPT_NO_F10) && !opt(OPT_H512_FWD_ON_TIER) && rs.B >= 1 && rs.T >= 1 && dtype == TTRNN_F32 && rs.cell == TTRNN_LSTM &&
          rs.hid_blocks <= 1 && rs.in != 1 && opt(OPT_FP32_MATH) == TTRNN_MATH_SPLIT &&
          (shape_matches<ShpH512R8L>(rs.hid_s) || shape_matches<ShpH384R8L>(rs.hid_s));
 }

@@ -1740,12 +1740,12 @@ int launch_t(const RnnShape& rs, const void* c0, const float* packed_hid, const 
   constexpr size_t lds = f10bh_lds_bytes<S>();
   static_assert(lds <= 150 * 1024, "LDS image set too large");
   const bool dg = opt(OPT_DIAG) != 0;
-  // (round 6) rank 8 at H = 256, one sample per CU: T01 and T2 wave-local, three barriers per step (option dev2 bit 10: the
+  // (round 6) rank 8 at H = 256, one sample per CU: T01 and T2 wave-local, three barriers per step (option f10bh_no_wl: the
   // four-barrier kernel, A/B)
   constexpr bool WL_OK = f10bh_ok<S>() && B::XF == 2 && F10<S>::R2 == 8 && B::NM2 * B::CT2 == FAST_NW && F10<S>::H == 256;
   if constexpr (WL_OK) {
-    const bool other = (f10bl_ok<S>() && (rs.B > device_cu_count() || (opt(OPT_DEV) & 128)) && !(opt(OPT_DEV) & 32768)) ||
-                       (opt(OPT_DEV) & (1 << 17)) || (opt(OPT_DEV2) & 1024);
+    const bool other = (f10bl_ok<S>() && (rs.B > device_cu_count() || opt(OPT_F10BL_ALWAYS)) && !opt(OPT_F10BL_NEVER)) ||
+                       opt(OPT_F10P) || opt(OPT_F10BH_NO_WL);
     if (!other) {
       hipLaunchKernelGGL((k_f10bh_prep<S, false, true>), dim3(B::FT + 1), dim3(FAST_NT), 0, stream, packed_hid, hdr, wfrag, bs.colmax,
                          bs.colmax ? 2 * 4 * B::H : 0);
@@ -1763,9 +1763,9 @@ int launch_t(const RnnShape& rs, const void* c0, const float* packed_hid, const 
     // one wave per 64 hidden units, T2 wave-local, two barriers per step: where two of its four-wave workgroups share a CU
     // (B > #CUs; cfg4: 586 -> 526 us per layer) and at H = 512 (eight waves either way).  One sample per CU at H = 256 stays on
     // the eight-wave kernel, whose phases are shorter than the four barriers cost (cfg2: 2 851 against 3 301 cycles per step).
-    // Option dev bit 15: the eight-wave kernel everywhere; bit 7: this kernel everywhere (A/B, the stamps of lesson 51)
-    const bool local = F10BL<S>::NWV != 4 || rs.B > device_cu_count() || (opt(OPT_DEV) & 128);
-    if (local && !(opt(OPT_DEV) & 32768)) {
+    // Option f10bl_never: the eight-wave kernel everywhere; f10bl_always: this kernel everywhere (A/B, the stamps of lesson 51)
+    const bool local = F10BL<S>::NWV != 4 || rs.B > device_cu_count() || opt(OPT_F10BL_ALWAYS);
+    if (local && !opt(OPT_F10BL_NEVER)) {
       constexpr size_t ldsl = f10bl_lds_bytes<S>();
       static_assert(ldsl <= 64 * 1024, "raise the dynamic LDS limit for this shape");
       auto kl = dg ? k_lstm_bwd_f10l<S, true> : k_lstm_bwd_f10l<S, false>;
@@ -1779,8 +1779,8 @@ int launch_t(const RnnShape& rs, const void* c0, const float* packed_hid, const 
     // the record-dependent half of the gate phase on the helper waves, one step ahead (k_lstm_bwd_f10p, round 5): MEASURED SLOWER
     // (cfg2 training step 1.689 against 1.642 ms; profiles/r5/stamps_cfg2_f10p.txt: the gate waves' phase stays at 670 cycles with
     // 45 instead of 75 instructions in it — it is made of the LDS round trips on either side of the barrier and the wave-maximum
-    // chain, not of the gate arithmetic — while the helper waves' split phase grows from 430 to 610).  Option dev bit 17 selects it.
-    if (opt(OPT_DEV) & (1 << 17)) {
+    // chain, not of the gate arithmetic — while the helper waves' split phase grows from 430 to 610).  Option f10p selects it.
+    if (opt(OPT_F10P)) {
       constexpr size_t ldsp = f10bp_lds_bytes<S>();
       static_assert(ldsp <= 150 * 1024, "LDS image set too large");
       auto kp = dg ? k_lstm_bwd_f10p<S, true> : k_lstm_bwd_f10p<S, false>;
@@ -1799,7 +1799,7 @@ int launch_t(const RnnShape& rs, const void* c0, const float* packed_hid, const 
                        (float*)d_c0, dg ? diag : nullptr, bs);
     return hipGetLastError() == hipSuccess ? TTRNN_OK : TTRNN_ERR_LAUNCH;
   } else {
-    return TTRNN_ERR_UNSUPPORTED;      // (H = 384: the wave-local kernel only; dev bit 15 has no eight-wave kernel to select)
+    return TTRNN_ERR_UNSUPPORTED;      // (H = 384: the wave-local kernel only; option f10bl_never has no eight-wave kernel to select)
   }
 }
 
@@ -1809,20 +1809,20 @@ bool f10bh_available(const RnnShape& rs, int dtype) {
   if (opt(OPT_GEMM_PIECES) == 3) return false;
   if (rs.cell == TTRNN_GRU)      // (bf16 storage: in every math mode, as the three-piece kernel; fp32 storage: split mode)
     return (dtype == TTRNN_BF16 || (dtype == TTRNN_F32 && opt(OPT_FP32_MATH) == TTRNN_MATH_SPLIT)) &&
-           (shape_matches<ShpH256R8G>(rs.hid_s) || (shape_matches<ShpH256R16G>(rs.hid_s) && !(opt(OPT_DEV2) & 128)));
+           (shape_matches<ShpH256R8G>(rs.hid_s) || (shape_matches<ShpH256R16G>(rs.hid_s) && !opt(OPT_GRU_R16_BWD_ON_TIER)));
   if (dtype != TTRNN_F32 || rs.cell != TTRNN_LSTM || opt(OPT_FP32_MATH) != TTRNN_MATH_SPLIT) return false;
   return shape_matches<ShpH256R8L>(rs.hid_s) || shape_matches<ShpH256R16L>(rs.hid_s);
 }
 
 // the reference's default benchmark shape (H = 512, r = 8): a runtime-tier shape whose reverse-time recurrence runs here in split
-// mode — eight gate waves, four feature tiles of T01 (K = 128) and two T2 pairs per wave (dev bit 16384 keeps the tier's kernel)
+// mode — eight gate waves, four feature tiles of T01 (K = 128) and two T2 pairs per wave (option h512_bwd_on_tier keeps the tier's kernel)
 // (round 5: H = 384, r = 8 — benchmarking.py --hidden_size 384 — on the wave-local kernel as six waves)
 // (round 6: the TT-GRU of the same benchmark — `--gru`: (8, 8, 8) x (8, 12, 16), K1 = 96 — on k_gru_bwd_f10h as eight gate waves;
-// option dev2 bit 8 keeps the tier's kernel)
+// option gru_h512_bwd_on_tier keeps the tier's kernel)
 bool f10bh_h512_available(const RnnShape& rs, int dtype) {
-  if (dtype != TTRNN_F32 || opt(OPT_FP32_MATH) != TTRNN_MATH_SPLIT || opt(OPT_GEMM_PIECES) == 3 || (opt(OPT_DEV) & 16384) || rs.T <= 0)
+  if (dtype != TTRNN_F32 || opt(OPT_FP32_MATH) != TTRNN_MATH_SPLIT || opt(OPT_GEMM_PIECES) == 3 || opt(OPT_H512_BWD_ON_TIER) || rs.T <= 0)
     return false;
-  if (rs.cell == TTRNN_GRU) return rs.hid_blocks <= 1 && shape_matches<ShpH512R8G>(rs.hid_s) && !(opt(OPT_DEV2) & 256);
+  if (rs.cell == TTRNN_GRU) return rs.hid_blocks <= 1 && shape_matches<ShpH512R8G>(rs.hid_s) && !opt(OPT_GRU_H512_BWD_ON_TIER);
   return rs.cell == TTRNN_LSTM && (shape_matches<ShpH512R8L>(rs.hid_s) || shape_matches<ShpH384R8L>(rs.hid_s));
 }
 size_t f10bh_h512_workspace_bytes() {
@@ -1873,10 +1873,10 @@ int launch_lstm_bwd_f10h(const RnnShape& rs, const void* c0, const float* packed
   return TTRNN_ERR_UNSUPPORTED;
 }
 
-// naive per-gate sets of H = 256, d = 3, r = 8 (fp32 storage, split mode; option dev2 bit 9 keeps the tier's kernel)
+// naive per-gate sets of H = 256, d = 3, r = 8 (fp32 storage, split mode; option naive_bwd_on_tier keeps the tier's kernel)
 bool f10n_bwd_available(const RnnShape& rs, int dtype) {
   return dtype == TTRNN_F32 && opt(OPT_FP32_MATH) == TTRNN_MATH_SPLIT && opt(OPT_GEMM_PIECES) != 3 && !opt(OPT_NO_F10) &&
-         !(opt(OPT_DEV2) & 512) && rs.B >= 1 && rs.T >= 1 && f10n_shape_matches(rs);
+         !opt(OPT_NAIVE_BWD_ON_TIER) && rs.B >= 1 && rs.T >= 1 && f10n_shape_matches(rs);
 }
 size_t f10n_bwd_workspace_bytes(const RnnShape& rs) {
   using B = F10BH<ShpH256N>;

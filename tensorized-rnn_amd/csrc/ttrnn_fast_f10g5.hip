@@ -210,7 +210,7 @@ __global__ void __launch_bounds__(F10G3<S>::NT * 64, 1) k_gru_fwd_f10g5(int B, i
 }
 
 bool f10g5_available(const RnnShape& rs, int dtype) {
-  return !opt(OPT_NO_F10) && !(opt(OPT_DEV) & 256) && rs.B >= 1 && rs.T >= 1 && dtype == TTRNN_F32 && rs.cell == TTRNN_GRU &&
+  return !opt(OPT_NO_F10) && !opt(OPT_GRU_FWD_ON_TIER) && rs.B >= 1 && rs.T >= 1 && dtype == TTRNN_F32 && rs.cell == TTRNN_GRU &&
          rs.hid_blocks <= 1 && rs.in != 1 && opt(OPT_FP32_MATH) == TTRNN_MATH_SPLIT && shape_matches<ShpH512R8G>(rs.hid_s);
 }
 size_t f10g5_workspace_bytes(const RnnShape& rs) {

@@ -294,10 +294,10 @@ int launch_gru_fwd_f10gh_g2(const RnnShape& rs, GinSrc src, const float* bilv, c
 // does this file's own plan (unit-row K-in + fused set-up launch, input_size == 1) exist for the shape?  (r = 8 only)
 bool f10gh_own_plan(const RnnShape& rs) { return shape_matches<ShpH256R8G>(rs.hid_s); }
 
-// fp32-storage TT-GRU, split math mode (dev bit 256: keep the runtime-shape tier's kernel, A/B)
+// fp32-storage TT-GRU, split math mode (option gru_fwd_on_tier: keep the runtime-shape tier's kernel, A/B)
 // (r = 16: behind the tier's K-in only, either input size; this file's own plan has no unit-row chain kernel for that shape)
 bool f10gh_available(const RnnShape& rs, int dtype) {
-  return !opt(OPT_NO_F10) && !(opt(OPT_DEV) & 256) && rs.B >= 1 && rs.T >= 1 && dtype == TTRNN_F32 && rs.cell == TTRNN_GRU &&
+  return !opt(OPT_NO_F10) && !opt(OPT_GRU_FWD_ON_TIER) && rs.B >= 1 && rs.T >= 1 && dtype == TTRNN_F32 && rs.cell == TTRNN_GRU &&
          rs.hid_blocks <= 1 && opt(OPT_FP32_MATH) == TTRNN_MATH_SPLIT &&
          (shape_matches<ShpH256R8G>(rs.hid_s) || shape_matches<ShpH256R16G>(rs.hid_s));
 }

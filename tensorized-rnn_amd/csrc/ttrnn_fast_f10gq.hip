@@ -24,7 +24,7 @@
 // k-blocks in two chains: the two kernels agree to fp32 rounding, not bit for bit).
 // MEASURED (cfg3, B = 256, T = 784): 0.678 ms against the eight-wave kernel's 0.570 — with one wave per SIMD nothing overlaps the
 // serial chain S2 -> barrier -> 24 MFMAs -> rotations -> two units' gates of each wave, and the two barriers saved do not pay
-// for it.  Kept as an A/B variant (option dev, bit 2), not dispatched by default.
+// for it.  Kept as an A/B variant (option f10gq_bf16), not dispatched by default.
 // Replaces tensorized_rnn/gru.py:33-44,124-134 with the hidden chain of t3nsor/ops.py:78-93 for the cfg3 shape.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>

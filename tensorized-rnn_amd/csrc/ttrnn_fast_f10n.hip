@@ -400,10 +400,10 @@ bool f10n_shape_matches(const RnnShape& rs) {
          f10n_joint_matches<ShpH256N>(rs.hid_s, f10n_gates(rs.cell));
 }
 
-// fp32-storage naive TT-LSTM / TT-GRU of H = 256, d = 3, r = 8 per gate, split math mode (dev bit 25: the runtime-shape tier's kernel, A/B)
+// fp32-storage naive TT-LSTM / TT-GRU of H = 256, d = 3, r = 8 per gate, split math mode (option naive_fwd_on_tier: the runtime-shape tier's kernel, A/B)
 bool f10n_available(const RnnShape& rs, int dtype) {
   const int G = f10n_gates(rs.cell);
-  return !opt(OPT_NO_F10) && !(opt(OPT_DEV) & (1 << 25)) && rs.B >= 1 && rs.T >= 1 && dtype == TTRNN_F32 &&
+  return !opt(OPT_NO_F10) && !opt(OPT_NAIVE_FWD_ON_TIER) && rs.B >= 1 && rs.T >= 1 && dtype == TTRNN_F32 &&
          (rs.cell == TTRNN_LSTM || rs.cell == TTRNN_GRU) && rs.hid_blocks == G && opt(OPT_FP32_MATH) == TTRNN_MATH_SPLIT &&
          f10n_joint_matches<ShpH256N>(rs.hid_s, G);
 }

@@ -206,14 +206,14 @@ static int launch_s(const RnnShape& rs, GinSrc gin, const void* h0, const void* 
   return hipGetLastError() == hipSuccess ? TTRNN_OK : TTRNN_ERR_LAUNCH;
 }
 
-// MEASURED SLOWER than the two-barrier kernel and therefore NOT the default (option dev bit 512 selects it, A/B): cfg2 0.495 against
+// MEASURED SLOWER than the two-barrier kernel and therefore NOT the default (option f10s selects it, A/B): cfg2 0.495 against
 // 0.478 ms (profiles/r5/stamps_cfg2_f10s.txt against stamps_cfg2_f10q.txt: the barrier it removes costs 88 + 111 -> 98 cycles, but
 // the gate wave's own chain grows — S10 673 -> 719, gates + S2 + stores 987 -> 1 076: eight chained S2 MFMAs, four crossbar gathers
 // and the splitting passes now sit behind the gate math of the SAME wave instead of being spread over the step's other half); the
 // eight-wave H = 512 instantiation spilled and lost 8 % (1.22 against 1.13 ms) and is not built.  DESIGN.md lesson 56.
 bool f10s_available(const RnnShape& rs, bool with_h0) {
   (void)with_h0;
-  if (!(opt(OPT_DEV) & 512)) return false;
+  if (!opt(OPT_F10S)) return false;
   return shape_matches<ShpH256R8L>(rs.hid_s);
 }
 

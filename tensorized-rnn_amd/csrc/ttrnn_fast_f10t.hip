@@ -1,6 +1,6 @@
 // ttrnn_fast_f10t.hip — the fused-core TT-LSTM forward kernel with cores 0·1 contracted FIRST (gfx950, rounds 7 and 8).
 // The kernel template is in ttrnn_f10t_kernel.h; this file instantiates its default time loop (ADJ = true, round 8, below),
-// ttrnn_fast_f10t_r7.hip round 7's loop (ADJ = false, option dev2 bit 4096).
+// ttrnn_fast_f10t_r7.hip round 7's loop (ADJ = false, option f10t_r7_loop).
 //
 // k_lstm_fwd_f10q keeps the reference's order: core 2 first (S2), then the fused core W10 = cores 1·0 (S10).  In that order every
 // wave needs ALL of C2 for its S10 tile: a 16 KB image in LDS, sixteen ds_read_b128 per wave and a barrier in front of them, every
@@ -40,20 +40,20 @@
 namespace ttrnn {
 
 // Default for cfg2's shape in split mode while every sample has a CU of its own (measured: profiles/r7/ab_cfg2_forward.txt);
-// option dev2 bit 2048 keeps k_lstm_fwd_f10q.  More samples than CUs (two workgroups per CU) stay on k_lstm_fwd_f10q: not measured.
+// option f10t_off keeps k_lstm_fwd_f10q.  More samples than CUs (two workgroups per CU) stay on k_lstm_fwd_f10q: not measured.
 bool f10t_available(const RnnShape& rs) {
-  if (opt(OPT_DEV2) & 2048) return false;
+  if (opt(OPT_F10T_OFF)) return false;
   return shape_matches<ShpH256R8L>(rs.hid_s) && rs.B <= device_cu_count();
 }
 
 // ws: the scale header of k_f10h_scale / the fused set-up launch (eu, ev); the old-order fragments behind it are not read.
-// Option dev2 bit 4096: round 7's time loop (fold across the wave's halves; ttrnn_fast_f10t_r7.hip) instead of the fold in the lane (A/B).
+// Option f10t_r7_loop: round 7's time loop (fold across the wave's halves; ttrnn_fast_f10t_r7.hip) instead of the fold in the lane (A/B).
 int launch_rnn_fwd_f10_t(const RnnShape& rs, GinSrc gin, const void* h0, const void* c0, const float* packed_hid,
                          const void* ws, const float* bias_hid, void* out, void* hT, void* cT, float* reserve,
                          hipStream_t stream) {
   using S = ShpH256R8L;
   if (!shape_matches<S>(rs.hid_s)) return TTRNN_ERR_UNSUPPORTED;
-  if (opt(OPT_DEV2) & 4096) return launch_rnn_fwd_f10_t_r7(rs, gin, h0, c0, packed_hid, ws, bias_hid, out, hT, cT, reserve, stream);
+  if (opt(OPT_F10T_R7_LOOP)) return launch_rnn_fwd_f10_t_r7(rs, gin, h0, c0, packed_hid, ws, bias_hid, out, hT, cT, reserve, stream);
   return launch_f10t<S, true>(rs, gin, h0, c0, packed_hid, reinterpret_cast<const float*>(ws), bias_hid, out, hT, cT, reserve, stream);
 }
 

@@ -1,5 +1,5 @@
 // ttrnn_fast_f10t_r7.hip — round 7's time loop of k_lstm_fwd_f10t (a unit's two fp16 pieces eight rows apart in stage 1's A operand,
-// one v_permlane32_swap per register to fold them), kept selectable behind option dev2 bit 4096 for A/B against the default loop of
+// one v_permlane32_swap per register to fold them), kept selectable behind option f10t_r7_loop for A/B against the default loop of
 // ttrnn_fast_f10t.hip.  A translation unit of its own because that file is built with -fno-slp-vectorize, under which THIS loop is
 // 1.3 % slower than it was (profiles/r8/ab_cfg2_f10t_loop.txt): here the plain flags, the code of round 7 instruction for instruction.
 #include "ttrnn_f10t_kernel.h"

@@ -1043,11 +1043,11 @@ static size_t dense_colmax_bytes(int in, int out) { return al256g((size_t)(in + 
 // tiles side by side on that XCD's L2).  Where the chip takes the tiles x ranges in ONE round, the largest such count; where it
 // does not — 72 tiles (768 x 3072: H = 768 hidden matrices) x 8 ranges = 576 workgroups ran as three rounds, the third a quarter
 // full — the count with the fewest rounds per range, a small charge per range for its partial tile and the reduction: 32 ranges
-// there (nine rounds of a quarter of the work: 2.16 -> ~1.7 ms), 24 for 18 tiles (384 x 1536).  (dev bit 28: the old rule.)
+// there (nine rounds of a quarter of the work: 2.16 -> ~1.7 ms), 24 for 18 tiles (384 x 1536).  (option dense_one_round_rule: the old rule.)
 static int dense_ks(int tiles, int cus) {
   const int up = ((cus / tiles + 7) / 8) * 8, dn = (cus / tiles) / 8 * 8;
   const int old_rule = (tiles * up <= cus || dn < 8) ? up : dn;
-  if (tiles * up <= cus || (opt(OPT_DEV) & (1 << 28))) return old_rule;
+  if (tiles * up <= cus || opt(OPT_DENSE_ONE_ROUND_RULE)) return old_rule;
   const int per_xcd = cus / 8 > 0 ? cus / 8 : 1;
   int best = old_rule;
   double bc = 1e30;
@@ -1151,7 +1151,7 @@ int launch_dense_wgrad(int dtype, int64_t n_rows, int in, int out, const void* x
   } while (0)
 #define TT_WG2(TSV, HV) do { if (rsh.T > 0) TT_WG(TSV, HV, true); else TT_WG(TSV, HV, false); } while (0)
 #ifdef TTRNN_ABLATIONS      // harness build only (`make ablation`): the no-MFMA / no-split / no-load / no-fragment-read instantiation
-  if (di == 4 && rsh.T == 0 && (opt(OPT_DEV) & (8 | 16 | 32 | 64))) {      // tools/wgrad_bench
+  if (di == 4 && rsh.T == 0 && (opt(OPT_DEV) & DEV_ABLATIONS)) {      // tools/wgrad_bench
     if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_dense_wgrad_split<float, true, false, true>), lds) != TTRNN_OK)
       return TTRNN_ERR_LAUNCH;
     hipLaunchKernelGGL((k_dense_wgrad_split<float, true, false, true>), dim3(grid), dim3(FAST_NT), lds, stream, n_rows, in, out,

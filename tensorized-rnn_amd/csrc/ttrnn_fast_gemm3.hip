@@ -322,7 +322,7 @@ __global__ void __launch_bounds__(FAST_NT) k_gemm3h(int64_t n_rows, int64_t n_pa
   }
 }
 
-// ---- the same GEMM as a PERSISTENT kernel (default; option `dev` bit 6 selects k_gemm3h<., 0> for A/B) --------------------------------
+// ---- the same GEMM as a PERSISTENT kernel (default; option gemm3_wg_per_tile selects k_gemm3h<., 0> for A/B) --------------------------------
 // One workgroup per CU walks over the tiles vb = blockIdx.x, + gridDim.x, ... of k_gemm3h's launch grid (same tile <-> XCD
 // mapping: the stride is a multiple of 8).  What the non-persistent kernel pays per tile — the wait for its 256 KB of output
 // stores before the workgroup may retire, the launch of the next workgroup, the latency of its first stage's DMAs with nothing
@@ -553,10 +553,10 @@ int launch_gemm3h(int dtype, int64_t n_rows, int K, int M, const void* x, const 
   } else {
     grid = 8 * ((RT + 7) / 8) * (int64_t)MT;
   }
-  // dev bit 0 (harness A/B): the ping-pong schedule.  Both schedules land within 3 % of each other (tools/gemm3_bench:
+  // option gemm3_pingpong (harness A/B): the ping-pong schedule.  Both schedules land within 3 % of each other (tools/gemm3_bench:
   // 2.25 / 2.31 ms without the output stores at cfg5's size = the 56-59 % of the f16 peak the chip sustains on random operands),
   // the lockstep one is ahead once the 2.1 GB of output stores are in
-  const bool var1 = (opt(OPT_DEV) & 1) == 0;
+  const bool var1 = !opt(OPT_GEMM3_PINGPONG);
 #define G3_LAUNCH(TSV, VARV)                                                                                               \
   do {                                                                                                                    \
     if (ensure_dynamic_lds(reinterpret_cast<const void*>(k_gemm3h<TSV, VARV>), G3_LDS) != TTRNN_OK) return TTRNN_ERR_LAUNCH; \
@@ -564,8 +564,8 @@ int launch_gemm3h(int dtype, int64_t n_rows, int K, int M, const void* x, const 
                        (const _Float16*)planes, (const _Float16*)xplanes, (const float*)wsc, (const float*)rs,            \
                        (const TSV*)bias, Hb, bias_ilv, y, opt(OPT_DEV));                                                  \
   } while (0)
-  // default: the persistent kernel (k_gemm3p), one workgroup per CU; dev bit 6: one workgroup per tile (A/B)
-  if (var1 && !(opt(OPT_DEV) & 64) && grid < (int64_t)1 << 30) {
+  // default: the persistent kernel (k_gemm3p), one workgroup per CU; option gemm3_wg_per_tile: one workgroup per tile (A/B)
+  if (var1 && !opt(OPT_GEMM3_WG_PER_TILE) && grid < (int64_t)1 << 30) {
     const int64_t pgrid = grid < (int64_t)device_cu_count() ? grid : (int64_t)device_cu_count() / 8 * 8;
 #define G3_LAUNCH_P(TSV, MT8V)                                                                                                  \
   do {                                                                                                                    \

@@ -312,13 +312,13 @@ bool proj4_shape(const TtShape& s, Proj3* p, Proj4* q) {
 // workspace: P | dP ([A][Mm][R2] floats each) | the PJ_NCH partial dG2
 size_t proj3_workspace_bytes(const TtShape& s) {
   Proj3 p;
-  if (opt(OPT_DEV) & 1024) return 0;             // A/B: the fused-core weight-gradient kernel on the unit rows, as before
+  if (opt(OPT_NO_PROJ3)) return 0;             // A/B: the fused-core weight-gradient kernel on the unit rows, as before
   Proj2 p2;
   if (proj2_shape(s, &p2)) return 256;           // d = 2: one launch, no scratch (a non-zero answer = "offered")
   Proj4 p4;
   size_t extra = 0;                               // d = 4: + the scratch packed cores and the scratch gradient [W0 | W1 | WQ] each
   if (proj4_shape(s, &p, &p4)) {
-    if (opt(OPT_DEV) & (1 << 23)) return 0;       // A/B: the any-shape chain kernel on the identity rows, as before
+    if (opt(OPT_NO_PROJ4)) return 0;       // A/B: the any-shape chain kernel on the identity rows, as before
     extra = 2 * (size_t)(p4.n01 + p4.nq);
   } else if (!proj3_shape(s, &p)) {
     return 0;

@@ -178,7 +178,7 @@ int launch_setup_t(const SetupArgs& a, hipStream_t stream) {
 
 // which (cell, shapes) have the fused set-up launch: fp32 storage, split math, input_size == 1, contiguous-or-strided fp32 cores
 bool f10_setup_available(const RnnShape& rs, int dtype) {
-  if (opt(OPT_DEV) & 1024 * 64) return false;
+  if (opt(OPT_NO_FUSED_SETUP)) return false;
   if (dtype != TTRNN_F32 || opt(OPT_FP32_MATH) != TTRNN_MATH_SPLIT || opt(OPT_NO_F10) || opt(OPT_NO_IN1) || rs.in != 1) return false;
   if (rs.cell == TTRNN_LSTM) return shape_matches<ShpH256R8L>(rs.hid_s) && shape_matches<ShpI1R8L>(rs.in_s);
   return f10gh_available(rs, dtype) && shape_matches<ShpI1R8G>(rs.in_s);

@@ -1393,7 +1393,7 @@ static int launch_bwd_w2g_t(const RnnShape& rs, const void* out, const void* h0,
 // the forward route of this file: fp32 storage, split fp32 math, a plain (not block-structured) TT-LSTM of the encoder's size
 bool w2_rnn_fwd_available(const RnnShape& rs, int dtype) {
   if (dtype != TTRNN_F32 || rs.hid_blocks > 1 || rs.H != 768 || rs.in != 40 || opt(OPT_FP32_MATH) != TTRNN_MATH_SPLIT ||
-      opt(OPT_FORCE_GENERIC) || opt(OPT_FORCE_G2) || (opt(OPT_DEV2) & 16))
+      opt(OPT_FORCE_GENERIC) || opt(OPT_FORCE_G2) || opt(OPT_ENC_FWD_ON_TIER))
     return false;
   if (rs.cell == TTRNN_GRU) return w2_config_gru(rs.hid_s, rs.in_s) > 0;
   return rs.cell == TTRNN_LSTM && w2_config(rs.hid_s, rs.in_s) > 0;
@@ -1429,7 +1429,7 @@ int launch_rnn_fwd_w2(const RnnShape& rs, const void* x, const void* h0, const v
 // reverse-time kernel of the same shapes (the forward's reserve format is everybody's: ttrnn_core.h res_gate / res_cell)
 bool w2_rnn_bwd_available(const RnnShape& rs, int dtype) {
   if (dtype != TTRNN_F32 || rs.hid_blocks > 1 || rs.H != 768 || rs.in != 40 || opt(OPT_FP32_MATH) != TTRNN_MATH_SPLIT ||
-      opt(OPT_FORCE_GENERIC) || opt(OPT_FORCE_G2) || (opt(OPT_DEV2) & 32))
+      opt(OPT_FORCE_GENERIC) || opt(OPT_FORCE_G2) || opt(OPT_ENC_BWD_ON_TIER))
     return false;
   if (rs.cell == TTRNN_GRU) return w2_config_gru(rs.hid_s, rs.in_s) > 0;
   return rs.cell == TTRNN_LSTM && w2_config(rs.hid_s, rs.in_s) > 0;

@@ -117,7 +117,7 @@ __global__ void __launch_bounds__(256) k_g2_merge(TtShape s, G2Mat m, const floa
 // The dense matrix of a TT-matrix from its merged cores, gate-interleaved like the chain kernel's output on identity rows
 // (ttrnn_mfma.h: ytile_index): W[j][hid * 4 + slot(g)] = sum_a Gh[i_h, j_h, a] Gt[i_t, j_t, a],  j = j_h J_t + j_t, o = g H + hid = i_h I_t + i_t.
 // K-in of the tier (input_size != 1) builds its dense matrix by running the any-shape chain kernel on the `in` identity rows: 83 us at the
-// reference's benchmark defaults (in = 256, 4H = 2048), 165 for a naive set's joint matrix; merge + this: ~10 (behind `dev` bit 24: see fwd_t).
+// reference's benchmark defaults (in = 256, 4H = 2048), 165 for a naive set's joint matrix; merge + this: ~10 (behind option g2_dense_from_merged: see fwd_t).
 __global__ void __launch_bounds__(256) k_g2_dense(G2Mat m, const float* __restrict__ Gh, const float* __restrict__ Gt,
                                                   float* __restrict__ W, int ldw, int H, int ilv) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1925,23 +1925,23 @@ static int in_pad(int in) { return (in + 7) & ~7; }
 // forward: the head fragments of every wave fit SIXTEEN register slots (and not eight): eight-wave plan, one stage-2 unit per wave
 static bool g2_fwd_res16(const G2Plan& p) {
   return p.hid.ok && p.okf && p.hid.nw == 8 && p.upt <= 2 && p.hid.UW == 1 && p.hid.KBP > G2_PF && p.hid.KBP <= 16 &&
-         !opt(OPT_DIAG) && !(opt(OPT_DEV) & 4096);       // (dev bit 12: A/B switch, the streamed kernel as before)
+         !opt(OPT_DIAG) && !opt(OPT_G2_FOUR_WAVE_STREAMED);       // (option g2_four_wave_streamed: A/B switch, the streamed kernel as before)
 }
 
 // reverse: every wave's head^T fragments stay in registers (one column tile, at most four live k-blocks per unit, G2_BSL slots)
 static bool g2_bwd_res(const G2Plan& p) {
-  // (several column tiles: resident since round 5 — dev bit 29: as before, one column tile only)
-  return p.hid.ok && p.okb && p.b_hun > 0 && (p.hid.N2T == 1 || (p.hid.N2T <= 4 && p.hid.bNP == 1 && !(opt(OPT_DEV) & (1 << 29)))) &&
+  // (several column tiles: resident since round 5 — option g2_bwd_one_tile: as before, one column tile only)
+  return p.hid.ok && p.okb && p.b_hun > 0 && (p.hid.N2T == 1 || (p.hid.N2T <= 4 && p.hid.bNP == 1 && !opt(OPT_G2_BWD_ONE_TILE))) &&
          p.hid.bNKBt <= 4 && p.hid.bUW * p.hid.bNKBt <= G2_BSL &&
-         !(opt(OPT_DEV) & 2048 && p.hid.ng > 1);
+         !(opt(OPT_G2_BWD_HEAD_STREAMED) && p.hid.ng > 1);
 }
 
 static bool g2_fwd_resident(const G2Plan& p);
 static void plan_for_single(G2Plan* p, const RnnShape& rs, bool backward) {
   const bool wide = rs.B <= device_cu_count();
-  // forward: column tiles inside a stage-2 unit where that makes a streamed head resident (G2Mat::cin; dev bit 27: never) — the plan of
+  // forward: column tiles inside a stage-2 unit where that makes a streamed head resident (G2Mat::cin; option g2_no_cin: never) — the plan of
   // the batch's own wave count first, the eight-wave plan where only it gets there
-  if (!backward && !(opt(OPT_DEV) & (1 << 27)) && !opt(OPT_DIAG)) {
+  if (!backward && !opt(OPT_G2_NO_CIN) && !opt(OPT_DIAG)) {
     G2Plan a, b8;
     g2_plan(&a, rs, wide, true);
     if (a.hid.ok && a.okf && a.hid.cin) { *p = a; return; }
@@ -1952,7 +1952,7 @@ static void plan_for_single(G2Plan* p, const RnnShape& rs, bool backward) {
       if (b8.hid.ok && b8.okf && b8.hid.cin && !(a0.hid.ok && a0.okf && g2_fwd_resident(a0))) { *p = b8; return; }
     }
   }
-  if (!wide && backward && !(opt(OPT_DEV) & 4096)) {
+  if (!wide && backward && !opt(OPT_G2_FOUR_WAVE_STREAMED)) {
     // the same trade in the reverse kernel: eight-wave workgroups with the head^T fragments resident (two rounds) instead of two
     // co-resident four-wave workgroups that stream them from L2 every step
     G2Plan q4, q8;
@@ -1969,10 +1969,10 @@ static void plan_for_single(G2Plan* p, const RnnShape& rs, bool backward) {
     if (g2_fwd_res16(q)) { *p = q; return; }
   }
   g2_plan(p, rs, wide);
-  if (!wide && backward && p->hid.ok && p->okb && !(opt(OPT_DEV) & (1 << 21))) {
+  if (!wide && backward && p->hid.ok && p->okb && !opt(OPT_G2_BWD_FOUR_WAVE)) {
     // four-wave workgroups are meant to run two per CU; where the reverse kernel's LDS leaves room for ONE, its four waves sit alone
     // on their SIMDs with nothing to hide the T2 loop's bookkeeping behind (--naive_tt: 47 000 of a step's 57 000 cycles, 370
-    // instructions per streamed block): the eight-wave plan instead, half the blocks per wave (dev bit 21: as before)
+    // instructions per streamed block): the eight-wave plan instead, half the blocks per wave (option g2_bwd_four_wave: as before)
     const int per_cu = G2_LDS_LIMIT / (p->b_lds + p->b_cmx + G2_LDS_STATIC);
     if (per_cu < 2) {
       G2Plan q8;
@@ -1987,12 +1987,12 @@ static void plan_for_single(G2Plan* p, const RnnShape& rs, bool backward) {
 }
 
 // forward, more samples than CUs, a head that no plan keeps in registers: TWO samples per workgroup share the stream (k_g2_fwd_p)
-// — where that kernel's images fit LDS (dev bit 19: A/B switch, one sample per workgroup as before)
+// — where that kernel's images fit LDS (option g2_pair_never: A/B switch, one sample per workgroup as before)
 static void plan_for(G2Plan* p, const RnnShape& rs, bool backward) {
   plan_for_single(p, rs, backward);
-  p->b_fast = (opt(OPT_DEV) & (1 << 22)) ? 0 : 1;      // (dev bit 22: the reverse kernel's streamed T2 on its general loop everywhere)
-  const bool any_b = (opt(OPT_DEV) & (1 << 20)) && rs.B >= 2;      // (dev bit 20: the tests' switch — pairs whatever the batch)
-  if (backward || (rs.B <= device_cu_count() && !any_b) || (opt(OPT_DEV) & (1 << 19))) return;
+  p->b_fast = opt(OPT_G2_BWD_T2_GENERAL) ? 0 : 1;      // (option g2_bwd_t2_general: the reverse kernel's streamed T2 on its general loop everywhere)
+  const bool any_b = opt(OPT_G2_PAIR_ALWAYS) && rs.B >= 2;      // (option g2_pair_always: the tests' switch — pairs whatever the batch)
+  if (backward || (rs.B <= device_cu_count() && !any_b) || opt(OPT_G2_PAIR_NEVER)) return;
   if (p->hid.ok && p->okf && (p->hid.UW * p->hid.KBP <= G2_PF || g2_fwd_res16(*p))) return;      // resident
   G2Plan q;
   g2_plan_pair(&q, rs);
@@ -2111,8 +2111,8 @@ static int fwd_t(const RnnShape& rs, const G2Plan& P, int dtype, const void* x, 
     if (hipMemsetAsync(wdense, 0, (size_t)inp * 4 * H * sizeof(float), stream) != hipSuccess) return TTRNN_ERR_LAUNCH;
     G2Mat mi;
     g2_plan_mat(&mi, rs.in_s, 4);
-    if (mi.ok && (opt(OPT_DEV) & (1 << 24))) {
-      // dev bit 24: the dense matrix from the merged cores (k_g2_merge + k_g2_dense, ~10 us) instead of the chain kernel on the identity rows
+    if (mi.ok && opt(OPT_G2_DENSE_FROM_MERGED)) {
+      // option g2_dense_from_merged: the dense matrix from the merged cores (k_g2_merge + k_g2_dense, ~10 us) instead of the chain kernel on the identity rows
       // (83 us at the benchmark defaults) — an A/B that showed no difference in the harness' eval time (1.28 / 1.26 ms, within the noise) and
       // moved one outlier case of test_split_math_outlier_up across its bound (another order of the sums): not the default
       float* Ghi = (float*)linws;
@@ -2291,7 +2291,7 @@ static int bwd_t(const RnnShape& rs, const G2Plan& P, const void* out, const voi
   const bool res = g2_bwd_res(P);
 #ifdef TTRNN_ABLATIONS
   G2Plan Pa = P;
-  Pa.abl = opt(OPT_DEV) & (8 | 16 | 32 | 64);
+  Pa.abl = opt(OPT_DEV) & DEV_ABLATIONS;
   if (getenv("TTRNN_G2_PLAN"))
     fprintf(stderr, "g2 bwd plan: nw %d s %d It %d Jt %d Ih %d Jh %d R %d ng %d | bM2T %d N2T %d bNKBt %d bUW %d bSW %d | bM1T %d N1T %d bKB1 %d bK1SPLIT %d | "
             "lds dy %d dc1 %d dh %d tab %d (hun %d) t1 %d cmx %d = %d | upt %d res %d\n", P.hid.nw, P.hid.s, P.hid.It, P.hid.Jt, P.hid.Ih,

@@ -103,10 +103,10 @@ int ttrnn_head_forward(const ttrnn_ttm* w, int dtype, int epilogue, int64_t n_ro
   int st = tt_shape_init(&s, w);
   if (st != TTRNN_OK) return st;
   // shapes on the any-shape forward kernel (the classifier heads: 256 -> 10 and the like): chain + epilogue in ONE launch (round 5;
-  // option dev bit 18: the separate epilogue launch, A/B)
+  // option head_split_epilogue: the separate epilogue launch, A/B)
   if (epilogue != TTRNN_EPI_NONE && n_rows > 0 && (dtype == TTRNN_F32 || dtype == TTRNN_BF16) && packed && x && y &&
       s.out_size <= 32 &&      // (one thread per row in there: ~4 serial passes over `out` LDS values — fine for 10, not for 256)
-      !(opt(OPT_DEV) & (1 << 18)) && (opt(OPT_FORCE_GENERIC) || !fast_ttlinear_fwd_available(s, dtype, 0))) {
+      !opt(OPT_HEAD_SPLIT_EPILOGUE) && (opt(OPT_FORCE_GENERIC) || !fast_ttlinear_fwd_available(s, dtype, 0))) {
     const LinPlan p = plan_ttlinear_fwd(s, n_rows);
     if (p.ws_bytes > 0 && (!workspace || workspace_bytes < p.ws_bytes)) return TTRNN_ERR_WORKSPACE;
     return launch_ttlinear_fwd(s, p, dtype, n_rows, packed, bias, x, y, workspace, (hipStream_t)stream, 0, 0, epilogue, aux);

@@ -197,7 +197,7 @@ int launch_rnn_fwd_f10_t(const RnnShape& rs, GinSrc gin, const void* h0, const v
                          hipStream_t stream);
 int launch_rnn_fwd_f10_t_r7(const RnnShape& rs, GinSrc gin, const void* h0, const void* c0, const float* packed_hid,
                             const void* ws, const float* bias_hid, void* out, void* hT, void* cT, float* reserve,
-                            hipStream_t stream);      // round 7's time loop (option dev2 bit 4096): ttrnn_fast_f10t_r7.hip
+                            hipStream_t stream);      // round 7's time loop (option f10t_r7_loop): ttrnn_fast_f10t_r7.hip
 int launch_rnn_fwd_f10_q(const RnnShape& rs, GinSrc gin, const void* h0, const void* c0, const float* packed_hid,
                            const void* wfrag, const float* bias_hid, void* out, void* hT, void* cT, float* reserve,
                            hipStream_t stream);
@@ -366,7 +366,7 @@ int launch_rnn_bwd_f10_h512(const RnnShape& rs, const void* out, const void* h0,
                             const float* reserve, const void* d_out, const void* d_hT, const void* d_cT, float* dg_in, float* dg_hid,
                             void* d_h0, void* d_c0, void* ws, hipStream_t stream, float* stats);
 // ttrnn_fast_proj.hip: d_packed += the adjoint of (three cores -> dense matrix) applied to dW (fp32 [in][out]); ws:
-// proj3_workspace_bytes (0: not offered for this shape / switched off by option dev bit 10)
+// proj3_workspace_bytes (0: not offered for this shape / switched off by option no_proj3)
 size_t proj3_workspace_bytes(const TtShape& s);
 int launch_proj3(const TtShape& s, const float* packed, const float* dW, float* d_packed, void* ws, hipStream_t stream);
 size_t f10bh_workspace_bytes(const RnnShape& rs);

@@ -3,6 +3,7 @@ C ABI on seeded operands, against a float64 evaluation of what it replaces: the 
 B*T rows (reference: tensorized_rnn/lstm.py:23-26, gru.py:33-36 -> t3nsor/layers.py:121-127 -> t3nsor/ops.py:78-93 under torch
 autograd).  The module-level parity of the same route against reference-generated fixtures is tests/test_gpu_parity.py
 (g6_bwd_spk*)."""
+import contextlib
 import ctypes
 
 import numpy as np
@@ -75,11 +76,13 @@ CASES = {
 BIG = {"spk_d4r3"}
 
 
-def _run(case, scale_dy=1.0, seed=3, poison=False, dev2=None):
+def _run(case, scale_dy=1.0, seed=3, poison=False, opts=None):
     from ttrnn_hip import _lib
-    if dev2 is None:
-        dev2 = 8 if case in BIG else 0
-    with _lib.option("dev2", dev2):
+    if opts is None:
+        opts = ("chain_wgrad_large",) if case in BIG else ()
+    with contextlib.ExitStack() as stack:
+        for name in opts:
+            stack.enter_context(_lib.option(name, 1))
         return _run_inner(case, scale_dy, seed, poison)
 
 
@@ -178,10 +181,10 @@ def test_chain_wgrad_gate_gradient_ranges(scale):
 
 @pytest.mark.parametrize("case", ["spk_lstm", "spk_lstm_h0", "spk_lstm_hid_only", "spk_gru", "spk_r4", "spk_d4r4", "spk_d4r2", "spk_d4r2_hid_only"])
 def test_image_kernel_still_takes_the_encoder_shapes(case):
-    """option dev2 bit 6 turns the register hand-off kernel (ttrnn_c2r_dev.h) off: k_c2w, the kernel with the C1 / dC1 images in
+    """option c2r_off turns the register hand-off kernel (ttrnn_c2r_dev.h) off: k_c2w, the kernel with the C1 / dC1 images in
     LDS, takes the same calls (the A/B of DESIGN.md 4c) to the same accuracy"""
-    dev2 = 64 | (8 if case in BIG else 0)
-    ref, got = _run(case, dev2=dev2)
+    opts = ("c2r_off",) + (("chain_wgrad_large",) if case in BIG else ())
+    ref, got = _run(case, opts=opts)
     for name in ("in", "hid"):
         if name not in got:
             continue
@@ -190,11 +193,11 @@ def test_image_kernel_still_takes_the_encoder_shapes(case):
 
 
 def test_run_time_plan_kernel_is_bit_identical_to_the_compile_time_instantiation():
-    """the speaker encoder's shapes run a kernel whose plan is a compile-time constant (c2_const_plan); option dev2 bit 2 selects
+    """the speaker encoder's shapes run a kernel whose plan is a compile-time constant (c2_const_plan); option c2_runtime_plan selects
     the same kernel with the plan at run time: same arithmetic, same order, same bits"""
     for case in ("spk_lstm_h0", "spk_lstm_hid_only", "spk_d4r2", "spk_d4r4_hid_only"):
-        _, a = _run(case, seed=11, dev2=64)
-        _, b = _run(case, seed=11, dev2=64 | 4)
+        _, a = _run(case, seed=11, opts=("c2r_off",))
+        _, b = _run(case, seed=11, opts=("c2r_off", "c2_runtime_plan"))
         for name in ("in", "hid"):
             if name in a:
                 for x, y in zip(a[name], b[name]):
@@ -226,7 +229,7 @@ def test_chain_route_is_offered_only_where_the_chain_is_cheaper():
     assert offered("lstm", spk["inp"], spk["hid"], 768, 3) and offered("lstm", spk["inp"], spk["hid"], 768, 2)
     assert not offered("lstm", ([1, 1, 1], [8, 8, 16], [1, 8, 8, 1]), ([4, 8, 8], [8, 8, 16], [1, 8, 8, 1]), 256)         # cfg2
     assert not offered("lstm", ([2, 4, 5], [8, 8, 16], [1, 16, 16, 1]), ([4, 8, 8], [8, 8, 16], [1, 16, 16, 1]), 256)     # cfg4
-    with _lib.option("dev2", 1):
+    with _lib.option("no_chain_wgrad", 1):
         assert not offered("lstm", spk["inp"], spk["hid"], 768, 3)
     # rank 4 at H = 768 and the four-core shapes need the kernel's large variant: offered where the plan has a compile-time
     # instantiation (ranks 2 and 4); other ranks (run-time plan of the large variant: slower than the dense gradient) are not

@@ -1,6 +1,6 @@
 """k_lstm_fwd_f10t (ttrnn_fast_f10t.hip): the fused-core TT-LSTM forward of H = 256, d = 3, r = 8 with cores 0·1 contracted first and
-the stage hand-off in registers — the default for that shape in split mode while a sample has a CU of its own; option dev2 bit
-2048 keeps k_lstm_fwd_f10q (core 2 first).  Through the module API, against the float64 oracle and against k_lstm_fwd_f10q:
+the stage hand-off in registers — the default for that shape in split mode while a sample has a CU of its own; option
+f10t_off keeps k_lstm_fwd_f10q (core 2 first).  Through the module API, against the float64 oracle and against k_lstm_fwd_f10q:
     out / h_T within 2e-6 and c_T within 4e-6 of float64 (the bounds of the single-barrier kernel's test), never more than twice
     k_lstm_fwd_f10q's own error + 1e-7, and within 5e-7 of k_lstm_fwd_f10q on out;
     repeat runs and batch subsets bit for bit; the final-state-only call; training forward = eval forward; gradients through the
@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 H = 256
 BS = (1, 3, 5)
 TS = (1, 2, 5, 33)
-F10Q = 2048          # option dev2: k_lstm_fwd_f10q for the calls k_lstm_fwd_f10t would take
+F10Q = "f10t_off"    # option: k_lstm_fwd_f10q for the calls k_lstm_fwd_f10t would take
 
 
 def dev():
@@ -75,7 +75,7 @@ def _assert_routes(m, B, T):
     from ttrnn_hip import functional as F
     assert F.rnn_route(_spec(m), B, T) == "fused_core"
     assert F.rnn_cores01_first(_spec(m), B, T)
-    with ttrnn_hip.option("dev2", F10Q):
+    with ttrnn_hip.option(F10Q, 1):
         assert F.rnn_route(_spec(m), B, T) == "fused_core"
         assert not F.rnn_cores01_first(_spec(m), B, T)
 
@@ -97,7 +97,7 @@ def test_forward_against_oracle_and_f10q(inp, with_state, bias, T):
         with torch.no_grad():
             new = m(xb, ib)
             again = m(xb, ib)
-            with ttrnn_hip.option("dev2", F10Q):
+            with ttrnn_hip.option(F10Q, 1):
                 old = m(xb, ib)
             last = m(xb, ib, need_outputs=False)              # OUT = false: the caller consumes only the final state
         en, eo = _maxabs(new[0], ro[:B]), _maxabs(old[0], ro[:B])
@@ -174,10 +174,10 @@ def _both_routes_vs_exact(m, x, h0, c0, label):
     with torch.no_grad():
         r64, (_, c64) = O.lstm_forward(layers, x.double(), (h0.double(), c0.double()))
     errs = {}
-    for name, mode, d2 in (("exact", "exact", 0), ("f10t", "split", 0), ("f10q", "split", F10Q)):
+    for name, mode, f10q in (("exact", "exact", 0), ("f10t", "split", 0), ("f10q", "split", 1)):
         with contextlib.ExitStack() as stack:
             stack.enter_context(ttrnn_hip.fp32_math(mode))
-            stack.enter_context(ttrnn_hip.option("dev2", d2))
+            stack.enter_context(ttrnn_hip.option(F10Q, f10q))
             if name == "f10t":
                 _assert_routes(m, B, T)
             with torch.no_grad():

@@ -1,6 +1,6 @@
 """k_lstm_fwd_f10t's two time loops (ttrnn_fast_f10t.hip): the default — a unit's two fp16 pieces on adjacent rows of stage 1's A
-operand, fold inside the lane — against round 7's loop (pieces eight rows apart, fold across the wave's halves), which option dev2
-bit 4096 keeps selectable in the same library.  Stage 2 sums in another k order, so the two are not bit-equal; the bounds are the
+operand, fold inside the lane — against round 7's loop (pieces eight rows apart, fold across the wave's halves), which option
+f10t_r7_loop keeps selectable in the same library.  Stage 2 sums in another k order, so the two are not bit-equal; the bounds are the
 ones tests/test_f10t.py uses between the two forward kernels:
     out / h_T within 2e-6 and c_T within 4e-6 of the float64 oracle, for BOTH loops;
     the default loop's error never more than twice round 7's + 1e-7; the two within 5e-7 of each other on out;
@@ -16,7 +16,7 @@ from test_f10t import TS, _assert_routes, _data, _maxabs, _module, _oracle, dev
 pytestmark = pytest.mark.gpu
 
 BS = (1, 3)
-R7_LOOP = 4096       # option dev2: round 7's time loop of k_lstm_fwd_f10t
+R7_LOOP = "f10t_r7_loop"       # option: round 7's time loop of k_lstm_fwd_f10t
 
 
 def _eq(a, b):
@@ -41,7 +41,7 @@ def test_default_loop_against_round7_loop(inp, with_state, bias, T):
             new = m(xb, ib)
             again = m(xb, ib)
             last = m(xb, ib, need_outputs=False)              # OUT = false: the caller consumes only the final state
-            with ttrnn_hip.option("dev2", R7_LOOP):
+            with ttrnn_hip.option(R7_LOOP, 1):
                 _assert_routes(m, B, T)                       # still k_lstm_fwd_f10t
                 old = m(xb, ib)
                 old_again = m(xb, ib)
@@ -64,7 +64,7 @@ def test_default_loop_against_round7_loop(inp, with_state, bias, T):
         # the training forward (reserve written) equals the eval forward bit for bit, in both loops
         tr = m(xb, ib)
         assert tr[0].requires_grad and torch.equal(tr[0].detach(), new[0]) and torch.equal(tr[1][1].detach(), new[1][1])
-        with ttrnn_hip.option("dev2", R7_LOOP):
+        with ttrnn_hip.option(R7_LOOP, 1):
             tr = m(xb, ib)
         assert tr[0].requires_grad and torch.equal(tr[0].detach(), old[0]) and torch.equal(tr[1][1].detach(), old[1][1])
         if full is None:

@@ -825,11 +825,11 @@ def test_naive_per_gate_sets_run_on_the_fused_path(kind, inp, H, L, d, r, B, T):
     lstm = kind == "ttlstm"
     # (round 5: the naive sets of H = 256, r = 8 have a fused-core forward kernel of their own, one gate per wave: ttrnn_fast_f10n.hip)
     assert F.rnn_route(m._all_layers[0]._layer_spec(), B, T) == ("fused_core" if (H == 256 and d == 3 and r == 8) else "runtime_mfma")
-    # (round 6: ... and a reverse-time kernel on the per-gate fused cores, k_rnn_bwd_f10n; option dev2 bit 9 = the tier's kernel)
+    # (round 6: ... and a reverse-time kernel on the per-gate fused cores, k_rnn_bwd_f10n; option naive_bwd_on_tier = the tier's kernel)
     first_tier = H == 256 and d == 3 and r == 8
     assert F.rnn_backward_route(m._all_layers[0]._layer_spec(), B, T) == ("fused_core" if first_tier else "runtime_mfma")
     import ttrnn_hip
-    with ttrnn_hip.option("dev2", 512):
+    with ttrnn_hip.option("naive_bwd_on_tier", 1):
         assert F.rnn_backward_route(m._all_layers[0]._layer_spec(), B, T) == "runtime_mfma"
     x = torch.randn(B, T, inp)
     w = torch.randn(B, T, H)
@@ -892,7 +892,7 @@ def test_naive_per_gate_sets_run_on_the_fused_path(kind, inp, H, L, d, r, B, T):
 def test_dense_gradient_pull_back_of_four_core_matrices(kind, inp, H, d, r, naive, B, T):
     """ttrnn_fast_proj.hip, d = 4 (round 5): the dense weight gradient dW = x^T dy of a four-core TT-matrix — a d = 4 layer, or the joint
     matrix of a naive per-gate set of three-core TTLinears (tt_linearset.py:5-38) — is pulled back onto the cores as (G0, G1, G2 G3)
-    through the three-core launches + one more, instead of the any-shape chain kernel on the identity rows (`dev` bit 23: as before).
+    through the three-core launches + one more, instead of the any-shape chain kernel on the identity rows (option no_proj4: as before).
     Every gradient against the oracle, the two routes against each other, and bitwise repeatable."""
     import ttrnn_hip
     torch.manual_seed(17)
@@ -915,7 +915,7 @@ def test_dense_gradient_pull_back_of_four_core_matrices(kind, inp, H, d, r, naiv
 
     new = grads()
     again = grads()
-    with ttrnn_hip.option("dev", 1 << 23):
+    with ttrnn_hip.option("no_proj4", 1):
         old = grads()
     seen = 0
     for name, g in new.items():
@@ -934,7 +934,7 @@ def test_dense_gradient_pull_back_of_four_core_matrices(kind, inp, H, d, r, naiv
 def test_paired_kernel_at_benchmark_size_is_bit_identical_to_single(kind, r, naive):
     """benchmarking.py's defaults with --naive_tt / --ttrank 16 (in = 256, H = 512, 160 steps) at a batch of 513 — more samples than
     CUs, odd: the DEFAULT route pairs them (the last workgroup holds one sample) — against the one-sample-per-workgroup kernel
-    (`dev` bit 19): outputs, final states and the training reserve (compared through the gradients of a masked loss) bit for bit."""
+    (option g2_pair_never): outputs, final states and the training reserve (compared through the gradients of a masked loss) bit for bit."""
     import ttrnn_hip
     from ttrnn_hip import functional as F
     torch.manual_seed(3)
@@ -958,7 +958,7 @@ def test_paired_kernel_at_benchmark_size_is_bit_identical_to_single(kind, r, nai
         return res[0].detach(), (res[1][0] if lstm else res[1]).detach(), {n: p.grad.clone() for n, p in m.named_parameters()}
 
     out2, h2, g2 = run()
-    with ttrnn_hip.option("dev", 1 << 19):
+    with ttrnn_hip.option("g2_pair_never", 1):
         assert F.rnn_samples_per_workgroup(spec, B, T) == 1
         out1, h1, g1 = run()
     assert torch.isfinite(out2).all()
@@ -971,7 +971,7 @@ def test_paired_kernel_at_benchmark_size_is_bit_identical_to_single(kind, r, nai
                                                    ("ttlstm", 40, 256, 3, 4, True), ("ttgru", 12, 768, 4, 6, False)])
 def test_tier_input_matrix_from_merged_cores(kind, inp, H, d, r, naive):
     """K-in of the runtime tier (input_size != 1) is a dense GEMM whose matrix is built from the TT cores at every launch, by the any-shape
-    chain kernel on the identity rows; `dev` bit 24 builds it from the MERGED cores instead (k_g2_merge + k_g2_dense: an A/B kept
+    chain kernel on the identity rows; option g2_dense_from_merged builds it from the MERGED cores instead (k_g2_merge + k_g2_dense: an A/B kept
     in the library, no measurable difference in the harness).  Same matrix up to the order of the sums: outputs within 2e-6 of each
     other, both within 1e-5 of the oracle."""
     import ttrnn_hip
@@ -987,7 +987,7 @@ def test_tier_input_matrix_from_merged_cores(kind, inp, H, d, r, naive):
         ro = (O.lstm_forward(layers, x) if kind == "ttlstm" else O.gru_forward(layers, x))[0]
         with ttrnn_hip.option("force_g2", 1):
             new = m(x.to(dev()))[0]
-            with ttrnn_hip.option("dev", 1 << 24):
+            with ttrnn_hip.option("g2_dense_from_merged", 1):
                 old = m(x.to(dev()))[0]
     assert _maxabs(new, ro) <= 1e-5 and _maxabs(old, ro) <= 1e-5
     assert _maxabs(new, old) <= 2e-6
@@ -999,7 +999,7 @@ def test_tier_input_matrix_from_merged_cores(kind, inp, H, d, r, naive):
 def test_naive_lstm_fused_core_kernel(inp, B, T, state, need_out):
     """k_rnn_fwd_f10n (ttrnn_fast_f10n.hip): the naive per-gate TT-LSTM (tt_linearset.py:5-38, tt_lstm.py:17-21; pmnist_test.py
     --naive_tt) of H = 256, d = 3, r = 8 on a fused-core kernel with ONE GATE PER WAVE, behind the runtime tier's K-in, instead of the
-    tier's own recurrent kernel (`dev` bit 25).  Outputs, final states and every per-gate gradient (the tier's reverse kernel reads the
+    tier's own recurrent kernel (option naive_fwd_on_tier).  Outputs, final states and every per-gate gradient (the tier's reverse kernel reads the
     reserve this kernel writes) against the oracle; the two forward kernels against each other; a false block promise is counted."""
     import ttrnn_hip
     from ttrnn_hip import functional as F
@@ -1008,7 +1008,7 @@ def test_naive_lstm_fused_core_kernel(inp, B, T, state, need_out):
     m = build_module(meta, dev())
     spec = m._all_layers[0]._layer_spec()
     assert F.rnn_route(spec, B, T) == "fused_core"
-    with ttrnn_hip.option("dev", 1 << 25):
+    with ttrnn_hip.option("naive_fwd_on_tier", 1):
         assert F.rnn_route(spec, B, T) == "runtime_mfma"
     x = torch.randn(B, T, inp)
     w = torch.randn(B, T, 256)
@@ -1040,7 +1040,7 @@ def test_naive_lstm_fused_core_kernel(inp, B, T, state, need_out):
     assert seen >= 24
     with torch.no_grad():
         fused = m(x.to(dev()), init, need_outputs=need_out) if not need_out else m(x.to(dev()), init)
-        with ttrnn_hip.option("dev", 1 << 25):
+        with ttrnn_hip.option("naive_fwd_on_tier", 1):
             tier = m(x.to(dev()), init, need_outputs=need_out) if not need_out else m(x.to(dev()), init)
     if need_out:
         assert torch.equal(fused[0], out.detach())                      # eval and training forwards: the same kernel, the same bits
@@ -1067,7 +1067,7 @@ def test_naive_lstm_fused_core_kernel(inp, B, T, state, need_out):
 def test_naive_gru_fused_core_kernel(inp, B, T, state):
     """The same kernel for the naive per-gate TT-GRU (three gate waves; gru.py:33-44,150-153: per-gate biases, the n gate's hidden bias
     inside r * (...)), H = 256, d = 3, r = 8: outputs, final state, every per-gate gradient against the oracle; against the tier's
-    kernel (`dev` bit 25); a decaying huge h_0 (the state's exponent is re-derived every step while it is positive)."""
+    kernel (option naive_fwd_on_tier); a decaying huge h_0 (the state's exponent is re-derived every step while it is positive)."""
     import ttrnn_hip
     from ttrnn_hip import functional as F
     torch.manual_seed(29)
@@ -1075,7 +1075,7 @@ def test_naive_gru_fused_core_kernel(inp, B, T, state):
     m = build_module(meta, dev())
     spec = m._all_layers[0]._layer_spec()
     assert F.rnn_route(spec, B, T) == "fused_core"
-    with ttrnn_hip.option("dev", 1 << 25):
+    with ttrnn_hip.option("naive_fwd_on_tier", 1):
         assert F.rnn_route(spec, B, T) == "runtime_mfma"
     x = torch.randn(B, T, inp)
     w = torch.randn(B, T, 256)
@@ -1103,7 +1103,7 @@ def test_naive_gru_fused_core_kernel(inp, B, T, state):
     assert seen >= 18
     with torch.no_grad():
         fused = m(x.to(dev()), init)
-        with ttrnn_hip.option("dev", 1 << 25):
+        with ttrnn_hip.option("naive_fwd_on_tier", 1):
             tier = m(x.to(dev()), init)
     assert torch.equal(fused[0], out.detach())
     assert _maxabs(fused[0], tier[0]) <= 2e-6 * max(1.0, float(ro.detach().abs().max()))
@@ -1115,7 +1115,7 @@ def test_naive_gru_fused_core_kernel(inp, B, T, state):
 def test_tier_column_tiles_inside_a_unit(kind, inp, H, d, r, B, T):
     """G2Mat::cin (round 5): with more than one column tile in stage 2 (I_t > 16: every d = 2 / d = 4 shape from H = 384 up, the speaker
     encoder's own H = 768, d = 2, r = 2) a forward unit is a ROW tile with its column tiles inside — one fragment, N2T accumulator pairs —
-    where that makes a streamed head resident; `dev` bit 27 = a unit per (row tile, column tile), as before.  The same products (the partial sums of a
+    where that makes a streamed head resident; option g2_no_cin = a unit per (row tile, column tile), as before.  The same products (the partial sums of a
     unit's k range may be split over the waves differently): against each other and against the oracle."""
     import ttrnn_hip
     torch.manual_seed(37)
@@ -1131,18 +1131,18 @@ def test_tier_column_tiles_inside_a_unit(kind, inp, H, d, r, B, T):
         ro = (O.lstm_forward(layers, x, (h0, c0)) if lstm else O.gru_forward(layers, x, h0))
         init = (h0.to(dev()), c0.to(dev())) if lstm else h0.to(dev())
         new = m(x.to(dev()), init)
-        with ttrnn_hip.option("dev", 1 << 27):
+        with ttrnn_hip.option("g2_no_cin", 1):
             old = m(x.to(dev()), init)
     if (kind, inp, H, d, r) == ("ttlstm", 40, 768, 2, 2):
         # the speaker encoder's own shape left the tier in round 6 (k_lstm_fwd_w2, ttrnn_fast_w2.hip): the first-tier route is what
-        # runs by default — checked against the oracle here — and option dev2 bit 4 brings the tier back for the comparison below
+        # runs by default — checked against the oracle here — and option enc_fwd_on_tier brings the tier back for the comparison below
         from ttrnn_hip import functional as F
         assert F.rnn_route(m._all_layers[0]._layer_spec(), B, T) == "fused_core"
         assert _maxabs(new[0], ro[0]) <= 1e-5
-        with torch.no_grad(), ttrnn_hip.option("dev2", 16):
+        with torch.no_grad(), ttrnn_hip.option("enc_fwd_on_tier", 1):
             assert F.rnn_route(m._all_layers[0]._layer_spec(), B, T) == "runtime_mfma"
             new = m(x.to(dev()), init)
-            with ttrnn_hip.option("dev", 1 << 27):
+            with ttrnn_hip.option("g2_no_cin", 1):
                 old = m(x.to(dev()), init)
     assert _maxabs(new[0], ro[0]) <= 1e-5 and _maxabs(old[0], ro[0]) <= 1e-5
     # (the two plans may split a unit's k range over the waves differently: same products, another order of the partial sums)
@@ -1167,7 +1167,7 @@ PAIR_CASES = [
 @pytest.mark.parametrize("kind,inp,H,d,r,naive,B,T,big_h0", PAIR_CASES)
 def test_runtime_tier_two_samples_per_workgroup(kind, inp, H, d, r, naive, B, T, big_h0):
     """k_g2_fwd_p: where the runtime tier streams the merged head from L2 every step and the batch exceeds the CU count, two samples
-    share a workgroup — and every streamed block (`--naive_tt` at H = 512: 512 KB per step).  `dev` bit 20 takes small batches there:
+    share a workgroup — and every streamed block (`--naive_tt` at H = 512: 512 KB per step).  option g2_pair_always takes small batches there:
     outputs, final states and the training reserve (through the gradients the reverse kernel derives from it) against the oracle,
     and BIT-identical to the one-sample-per-workgroup kernel (same products, same order, per sample)."""
     import ttrnn_hip
@@ -1204,12 +1204,12 @@ def test_runtime_tier_two_samples_per_workgroup(kind, inp, H, d, r, naive, B, T,
 
     assert F.rnn_route(spec, B, T) == "runtime_mfma"
     assert F.rnn_samples_per_workgroup(spec, B, T) == 1
-    with ttrnn_hip.option("dev", 1 << 20):
+    with ttrnn_hip.option("g2_pair_always", 1):
         assert F.rnn_samples_per_workgroup(spec, B, T) == 2
         assert F.rnn_samples_per_workgroup(spec, 1, T) == 1
         res, xg = run(True)
         grads = {n: p.grad.clone() for n, p in m.named_parameters()}
-        with ttrnn_hip.option("dev", (1 << 20) | (1 << 19)):
+        with ttrnn_hip.option("g2_pair_never", 1):
             assert F.rnn_samples_per_workgroup(spec, B, T) == 1
     out = res[0].detach()
     assert _maxabs(out, ro.detach()) <= 1e-5 * max(1.0, float(ro.detach().abs().max()))
@@ -1271,7 +1271,7 @@ def test_dtype_and_device_mismatches_are_refused():
 
 def test_gru_four_wave_kernel_matches_eight_wave_kernel_and_oracle():
     """The bf16 TT-GRU shape (cfg3) on the four-wave kernel whose lanes hold r, z, n of their own units (three rotated
-    MFMA tiles per pair of unit rows, ttrnn_fast_f10gq.hip; an A/B variant behind option dev bit 2 — it measured slower than
+    MFMA tiles per pair of unit rows, ttrnn_fast_f10gq.hip; an A/B variant behind option f10gq_bf16 — it measured slower than
     the default) against the eight-wave kernel with its LDS gate vector and the fp32 oracle: forward with an initial state, input_size 1 and 40 (the scalar shortcut and the hoisted
     projection), and the gradients the forward's reserve feeds."""
     import ttrnn_hip
@@ -1283,9 +1283,9 @@ def test_gru_four_wave_kernel_matches_eight_wave_kernel_and_oracle():
         h0 = (torch.randn(B, 256) * 0.5).to(torch.bfloat16)
         w = torch.randn(B, T, 256, device=dev())
         res = {}
-        for name, devbits in (("four", 4), ("eight", 0)):
+        for name, f10gq in (("four", 1), ("eight", 0)):
             m.zero_grad()
-            with ttrnn_hip.option("dev", devbits):
+            with ttrnn_hip.option("f10gq_bf16", f10gq):
                 xg = x.to(dev()).requires_grad_(True)
                 out, hT = m(xg, h0.to(dev()))
                 (out.float() * w).sum().backward()
@@ -2882,7 +2882,7 @@ def test_fused_core_half_piece_reverse_kernel_outlier_weights(rank, which, facto
 def test_fused_core_gru_reverse_kernel_rank_16(case, inp):
     """round 6: `benchmarking.py --hidden_size 256 --gru --ttrank 16` — the TT-GRU of rank 16 on the two-piece
     fused-core reverse-time kernel (k_gru_bwd_f10h<ShpH256R16G>: twelve T2 pairs, two per wave on waves 0-3) instead of the stage-wise
-    kernel; against the float64 oracle and against the route it replaces (option dev2 bit 7) reading the same forward records."""
+    kernel; against the float64 oracle and against the route it replaces (option gru_r16_bwd_on_tier) reading the same forward records."""
     import ttrnn_hip
     from ttrnn_hip import functional as F
     from oracle import ttrnn_oracle as O
@@ -2900,7 +2900,7 @@ def test_fused_core_gru_reverse_kernel_rank_16(case, inp):
         w[:, :-1] = 0.0
     spec = m._all_layers[0]._layer_spec()
     assert F.rnn_backward_route(spec, B, T) == "fused_core"
-    with ttrnn_hip.option("dev2", 128):
+    with ttrnn_hip.option("gru_r16_bwd_on_tier", 1):
         assert F.rnn_backward_route(spec, B, T) != "fused_core"
     sd = {k: v.detach().cpu().double() for k, v in m.state_dict().items()}
     layers, leaves = O.layers_from_state_dict(sd, 1, requires_grad=True, dtype=torch.float64)
@@ -2918,7 +2918,7 @@ def test_fused_core_gru_reverse_kernel_rank_16(case, inp):
 
     got = run()
     again = run()
-    with ttrnn_hip.option("dev2", 128):
+    with ttrnn_hip.option("gru_r16_bwd_on_tier", 1):
         old = run()
     refs = {"h0": h0r.grad, "x": xr.grad, **{n: leaves[n].grad for n, _ in m.named_parameters()}}
     worst = {"fused": 0.0, "replaced": 0.0}
@@ -2938,7 +2938,7 @@ def test_naive_sets_reverse_kernel(kind, case):
     """round 6: the naive per-gate sets of H = 256, d = 3, r = 8 (tt_linearset.py:5-38; pMNIST --naive_tt [--gru])
     on a reverse-time kernel of their own — k_rnn_bwd_f10n: T01 per gate on the gate's fused core, T2 over all gates' k-blocks — instead
     of the tier's kernel on the joint matrix.  Every gradient against the float64 oracle (per-gate evaluation) and against the route
-    it replaces (option dev2 bit 9) reading the same forward records; output gradients over ten decades, steps and samples without
+    it replaces (option naive_bwd_on_tier) reading the same forward records; output gradients over ten decades, steps and samples without
     gradient, a loss on the last step only, no initial state, one core entry x 1e3, and the benchmark's size (B = 64, T = 784:
     against the tier, and twice for the bits)."""
     import ttrnn_hip
@@ -2992,7 +2992,7 @@ def test_naive_sets_reverse_kernel(kind, case):
         return g
 
     got, again = run(), run()
-    with ttrnn_hip.option("dev2", 512):
+    with ttrnn_hip.option("naive_bwd_on_tier", 1):
         assert F.rnn_backward_route(spec, B, T) == "runtime_mfma"
         old = run()
     for n in got:
@@ -3040,7 +3040,7 @@ def test_naive_sets_reverse_kernel(kind, case):
 def test_fused_core_gru_reverse_kernel_h512(case):
     """round 6: the reference's benchmark defaults with --gru (TT-GRU in = 256, H = 512, d = 3, r = 8) — the
     reverse-time recurrence on k_gru_bwd_f10h<ShpH512R8G> (eight gate waves, K1 = 96, sixteen T2 pairs) instead of the tier's kernel;
-    against the float64 oracle and against the route it replaces (option dev2 bit 8) reading the same forward records."""
+    against the float64 oracle and against the route it replaces (option gru_h512_bwd_on_tier) reading the same forward records."""
     import ttrnn_hip
     from ttrnn_hip import functional as F
     from oracle import ttrnn_oracle as O
@@ -3058,7 +3058,7 @@ def test_fused_core_gru_reverse_kernel_h512(case):
         w[:, :-1] = 0.0
     spec = m._all_layers[0]._layer_spec()
     assert F.rnn_backward_route(spec, B, T) == "fused_core"
-    with ttrnn_hip.option("dev2", 256):
+    with ttrnn_hip.option("gru_h512_bwd_on_tier", 1):
         assert F.rnn_backward_route(spec, B, T) == "runtime_mfma"
     sd = {k: v.detach().cpu().double() for k, v in m.state_dict().items()}
     layers, leaves = O.layers_from_state_dict(sd, 1, requires_grad=True, dtype=torch.float64)
@@ -3081,7 +3081,7 @@ def test_fused_core_gru_reverse_kernel_h512(case):
 
     got = run()
     again = run()
-    with ttrnn_hip.option("dev2", 256):
+    with ttrnn_hip.option("gru_h512_bwd_on_tier", 1):
         old = run()
     refs = {"x": xr.grad, **{n: leaves[n].grad for n, _ in m.named_parameters()}}
     if h0r is not None:
@@ -3161,7 +3161,7 @@ def test_fused_core_half_piece_gru_reverse_kernel_ranges(case, dtype):
 
 def test_gru_forward_kernel_with_in_wave_s2_matches_eight_wave_kernel_and_oracle():
     """cfg3's default forward kernel (k_gru_fwd_f10v: four waves, the S2 operand gathered inside the gate waves with one DPP shift
-    and one ds_bpermute per lane) against the eight-wave kernel it replaced (option dev bit 5) and the fp32 oracle: the two
+    and one ds_bpermute per lane) against the eight-wave kernel it replaced (option gru_eight_wave) and the fp32 oracle: the two
     kernels multiply the same bf16 operands and differ by at most one bf16 ulp of an intermediate; gin-fed layers (stacked,
     input_size 40), h_0 given, training forward (reserve) included."""
     import ttrnn_hip
@@ -3176,8 +3176,8 @@ def test_gru_forward_kernel_with_in_wave_s2_matches_eight_wave_kernel_and_oracle
         layers, _ = O.layers_from_state_dict(sd, L)
         ro, rh = O.gru_forward(layers, x.float(), h0.float() if with_h0 else None)
         outs = {}
-        for name, d in (("in_wave", 0), ("eight_wave", 32)):
-            with ttrnn_hip.option("dev", d), torch.no_grad():
+        for name, on in (("in_wave", 0), ("eight_wave", 1)):
+            with ttrnn_hip.option("gru_eight_wave", on), torch.no_grad():
                 outs[name] = m(x.to(dev()), h0.to(dev()) if with_h0 else None)
         a, b = outs["in_wave"][0].float(), outs["eight_wave"][0].float()
         assert torch.isfinite(a).all()
@@ -3193,7 +3193,7 @@ def test_gru_forward_kernel_with_in_wave_s2_matches_eight_wave_kernel_and_oracle
 @pytest.mark.parametrize("H,inp,B,T,with_state", [(256, 1, 9, 60, False), (256, 1, 70, 33, True), (256, 40, 300, 12, True)])
 def test_single_barrier_forward_kernel_matches_two_barrier_kernel_and_oracle(H, inp, B, T, with_state):
     """k_lstm_fwd_f10s (ttrnn_fast_f10s.hip, round 5: S2 of the new state inside the gate waves, ONE barrier per step; measured
-    3.5 % slower than the two-barrier kernel on cfg2 and kept behind option dev bit 9 as the A/B record of DESIGN.md lesson 56)
+    3.5 % slower than the two-barrier kernel on cfg2 and kept behind option f10s as the A/B record of DESIGN.md lesson 56)
     against the default kernel and the float64 oracle: same scales, same S10; S2 sums its four terms in two chained MFMAs instead
     of one, so the two kernels agree to an ulp of an accumulator, and neither is further from float64 than the other.  Training
     forward (reserve) + backward included; batch rows independent, repeatable."""
@@ -3211,8 +3211,8 @@ def test_single_barrier_forward_kernel_matches_two_barrier_kernel_and_oracle(H, 
     assert F.rnn_route(m._all_layers[0]._layer_spec(), B, T) == "fused_core"
     di = None if init is None else tuple(t.to(dev()) for t in init)
     outs = {}
-    for name, d in (("one_barrier", 512), ("two_barriers", 0)):
-        with ttrnn_hip.option("dev", d), torch.no_grad():
+    for name, on in (("one_barrier", 1), ("two_barriers", 0)):
+        with ttrnn_hip.option("f10s", on), torch.no_grad():
             outs[name] = m(x.to(dev()), di)
     a, b_ = outs["one_barrier"], outs["two_barriers"]
     ea, eb = _maxabs(a[0], ro), _maxabs(b_[0], ro)
@@ -3222,7 +3222,7 @@ def test_single_barrier_forward_kernel_matches_two_barrier_kernel_and_oracle(H, 
     assert _maxabs(a[1][0], rh) <= 2e-6 and _maxabs(a[1][1], rc) <= 4e-6
     w = torch.randn(B, T, H)
     ((ro * w.double()).sum() + 0.5 * rh.sum() + 0.25 * rc.sum()).backward()
-    with ttrnn_hip.option("dev", 512):
+    with ttrnn_hip.option("f10s", 1):
         with torch.no_grad():
             again = m(x.to(dev()), di)
             sub = m(x[[2, 0]].to(dev()), None if di is None else (di[0][[2, 0]], di[1][[2, 0]]))
@@ -3246,7 +3246,7 @@ def test_fused_setup_launch_is_bit_identical(kind):
     """ABI 6: ttrnn_rnn_forward_cores on the input_size == 1 fused-core shapes (cfg2's TT-LSTM, the fp32 TT-GRU) does packing, the
     unit-row input projection, the scale header and the MFMA fragments in ONE set-up launch (ttrnn_fast_setup.hip) instead of four.
     Same expressions as the kernels it replaces: outputs, final states, the packed cores and EVERY gradient must be bit-identical
-    to the separate launches (option dev bit 16 switches the fused launch off) — strided Parameters (the reference's layout),
+    to the separate launches (option no_fused_setup switches the fused launch off) — strided Parameters (the reference's layout),
     non-contiguous after an in-place update, with and without biases and initial states."""
     import ctypes
     import ttrnn_hip
@@ -3264,9 +3264,9 @@ def test_fused_setup_launch_is_bit_identical(kind):
         init = None if h0 is None else ((h0, torch.randn(B, 256, device=dev())) if kind == "ttlstm" else h0)
         desc = m._all_layers[0]._layer_spec().desc(B, T, 0)
         res = {}
-        for name, d in (("fused", 0), ("separate", 65536)):
-            with ttrnn_hip.option("dev", d):
-                assert _lib.load().ttrnn_rnn_forward_cores_fused(ctypes.byref(desc)) == (1 if d == 0 else 0)
+        for name, on in (("fused", 0), ("separate", 1)):
+            with ttrnn_hip.option("no_fused_setup", on):
+                assert _lib.load().ttrnn_rnn_forward_cores_fused(ctypes.byref(desc)) == (1 if not on else 0)
                 with torch.no_grad():
                     r = m(x, init)
                 m.zero_grad()
@@ -3288,7 +3288,7 @@ def test_fused_setup_launch_is_bit_identical(kind):
 
 @pytest.mark.parametrize("rank,inp,with_state", [(8, 1, False), (8, 40, True), (16, 40, True)])
 def test_reverse_kernel_with_precomputed_gate_factors(rank, inp, with_state):
-    """k_lstm_bwd_f10p (round 5 A/B kernel, option dev bit 17: waves 4-7 turn the forward record into the gate-gradient factors
+    """k_lstm_bwd_f10p (round 5 A/B kernel, option f10p: waves 4-7 turn the forward record into the gate-gradient factors
     one step ahead, waves 0-3 run seven multiply-adds per unit; measured 3 % slower than k_lstm_bwd_f10h and not the default —
     DESIGN.md lesson 57) against the default reverse kernel and the float64 oracle: every gradient incl. d_h0 / d_c0 and the
     by-products' consumers (bias gradients, input_size == 1 sums), repeatable, masked samples exactly zero."""
@@ -3309,8 +3309,8 @@ def test_reverse_kernel_with_precomputed_gate_factors(rank, inp, with_state):
     wfin[[2, 40]] = 0.0
     ((ro * w.double()).sum() + 0.5 * (rh * wfin).sum() + 0.25 * (rc * wfin).sum()).backward()
 
-    def run(d):
-        with ttrnn_hip.option("dev", d):
+    def run(f10p):
+        with ttrnn_hip.option("f10p", f10p):
             m.zero_grad()
             di = None if init is None else tuple(t.to(dev()).requires_grad_(True) for t in init)
             out, (hT, cT) = m(x.to(dev()), di)
@@ -3321,7 +3321,7 @@ def test_reverse_kernel_with_precomputed_gate_factors(rank, inp, with_state):
                 g["h0"], g["c0"] = di[0].grad.clone(), di[1].grad.clone()
             return g
 
-    got, again, other = run(1 << 17), run(1 << 17), run(0)
+    got, again, other = run(1), run(1), run(0)
     refs = {n: leaves[n].grad for n, _ in m.named_parameters()}
     if ir is not None:
         refs["h0"], refs["c0"] = ir[0].grad, ir[1].grad
@@ -3344,7 +3344,7 @@ def test_gru_fp32_fused_core_error_vs_fp64_is_fp32_class():
     """The reference's GRU is fp32 only (tensorized_rnn/gru.py:25-50).  Its cfg3 shape on the two-piece fused-core kernel
     (k_gru_fwd_f10vh, ttrnn_fast_f10gh.hip: the default of the split mode since round 5) over the full 784 steps against the
     oracle evaluated in float64: as close to the exact result as ordinary fp32 arithmetic (the fp32-MFMA mode and the torch-CPU
-    fp32 oracle); the runtime-shape tier's kernel (option dev bit 8: the route fp32 GRUs took until round 4) beside it."""
+    fp32 oracle); the runtime-shape tier's kernel (option gru_fwd_on_tier: the route fp32 GRUs took until round 4) beside it."""
     import ttrnn_hip
     from ttrnn_hip import functional as F
     m = _cfg3_fp32_module()
@@ -3354,8 +3354,8 @@ def test_gru_fp32_fused_core_error_vs_fp64_is_fp32_class():
     r64, h64, _ = _oracle_forward("ttgru", sd, 1, x.double())
     r32, h32, _ = _oracle_forward("ttgru", sd, 1, x)
     errs = {"cpu_fp32": _maxabs(r32, r64)}
-    for mode, d in (("exact", 0), ("split", 0), ("tier", 256)):
-        with ttrnn_hip.fp32_math("exact" if mode == "exact" else "split"), ttrnn_hip.option("dev", d), torch.no_grad():
+    for mode, on in (("exact", 0), ("split", 0), ("tier", 1)):
+        with ttrnn_hip.fp32_math("exact" if mode == "exact" else "split"), ttrnn_hip.option("gru_fwd_on_tier", on), torch.no_grad():
             route = F.rnn_route(m._all_layers[0]._layer_spec(), 4, 784)
             assert route == {"exact": "stagewise_mfma", "split": "fused_core", "tier": "runtime_mfma"}[mode], (mode, route)
             out, hT = m(x.to(dev()))
@@ -3437,7 +3437,7 @@ def test_gru_fp32_fused_core_operand_ranges(case):
 
 def test_gru_fp32_fused_core_variants_vs_oracle_and_tier():
     """k_gru_fwd_f10vh's template variants — input_size 1 / gin-fed (input_size 40, stacked layers), h_0 given or not, `out`
-    skipped (the classifier reads only the last step) — against the fp32 oracle and the runtime-shape tier's kernel (dev bit 8),
+    skipped (the classifier reads only the last step) — against the fp32 oracle and the runtime-shape tier's kernel (option gru_fwd_on_tier),
     plus the training forward (reserve) feeding the reverse-time kernel k_gru_bwd_f10h: every gradient against the oracle's
     autograd in float64."""
     import ttrnn_hip
@@ -3457,9 +3457,9 @@ def test_gru_fp32_fused_core_variants_vs_oracle_and_tier():
         xr = x.double().clone().requires_grad_(True)
         ro, rh = O.gru_forward(layers, xr, h0.double() if with_h0 else None)
         outs = {}
-        for name, d in (("fused", 0), ("tier", 256)):
-            with ttrnn_hip.option("dev", d), torch.no_grad():
-                assert F.rnn_route(m._all_layers[-1]._layer_spec(), B, T) == ("fused_core" if d == 0 else "runtime_mfma")
+        for name, on in (("fused", 0), ("tier", 1)):
+            with ttrnn_hip.option("gru_fwd_on_tier", on), torch.no_grad():
+                assert F.rnn_route(m._all_layers[-1]._layer_spec(), B, T) == ("fused_core" if not on else "runtime_mfma")
                 outs[name] = m(x.to(dev()), h0.to(dev()) if with_h0 else None)
         assert _maxabs(outs["fused"][0], ro) <= 1e-5 and _maxabs(outs["fused"][1], rh) <= 1e-5
         assert _maxabs(outs["fused"][0], outs["tier"][0]) <= 2e-6
@@ -3486,7 +3486,7 @@ def test_gru_h512_gates_on_accumulators_kernel(inp, B, T, h0_scale):
     """k_gru_fwd_f10g5 (ttrnn_fast_f10g5.hip, round 5): the reference's benchmark defaults with --gru (benchmarking.py:75-83:
     TT-GRU H = 512, d = 3, rank 8 — out modes (8, 12, 16): r, z, n of a unit share a column of the fused core, 32 rows apart), gates on
     the accumulators as in the TT-LSTM kernels, behind the runtime tier's dense K-in.  Against the float64 oracle and the tier's own
-    recurrent kernel (option dev bit 8); h_0 inside and far outside (-1, 1); final-state-only calls; training forward feeding the
+    recurrent kernel (option gru_fwd_on_tier); h_0 inside and far outside (-1, 1); final-state-only calls; training forward feeding the
     tier's reverse kernel: every gradient against the oracle's float64 autograd."""
     import ttrnn_hip
     from ttrnn_hip import functional as F
@@ -3503,9 +3503,9 @@ def test_gru_h512_gates_on_accumulators_kernel(inp, B, T, h0_scale):
     ro, rh = O.gru_forward(layers, xr, None if h0 is None else h0.double())
     scale = max(1.0, float(ro.abs().max()))
     outs = {}
-    for name, d in (("fused", 0), ("tier", 256)):
-        with ttrnn_hip.option("dev", d), torch.no_grad():
-            assert F.rnn_route(m._all_layers[0]._layer_spec(), B, T) == ("fused_core" if d == 0 else "runtime_mfma")
+    for name, on in (("fused", 0), ("tier", 1)):
+        with ttrnn_hip.option("gru_fwd_on_tier", on), torch.no_grad():
+            assert F.rnn_route(m._all_layers[0]._layer_spec(), B, T) == ("fused_core" if not on else "runtime_mfma")
             outs[name] = m(x.to(dev()), None if h0 is None else h0.to(dev()))
     ef, et = _maxabs(outs["fused"][0], ro), _maxabs(outs["tier"][0], ro)
     print("TT-GRU H=512 in=%d B=%d h0=%s: max abs error vs float64 fused %.3g tier %.3g (state scale %.3g)" % (inp, B, h0_scale, ef, et, scale))
@@ -3655,7 +3655,7 @@ def test_two_core_reverse_kernel_ranges(case):
 def test_h512_fused_core_forward_route(B, T, inp, with_state, H):
     """The reference's default benchmark shape (benchmarking.py:75-83: TT-LSTM hidden 512, ncores 3, ttrank 8): in split mode the
     forward recurrent kernel is the fused-core kernel as eight-wave workgroups (k_lstm_fwd_f10q<ShpH512R8L>) behind the runtime tier's
-    dense K-in; exact mode and option dev bit 13 keep the runtime-shape / any-shape kernels.  Round 5: the same for --hidden_size 384
+    dense K-in; exact mode and option h512_fwd_on_tier keep the runtime-shape / any-shape kernels.  Round 5: the same for --hidden_size 384
     (out modes (8, 12, 16): six S10 tiles = six waves, the 24 S2 tiles dealt out one by one, a 48-slot image row swizzled in blocks
     of sixteen).  Outputs and every gradient (the reverse
     kernel is the runtime tier's, reading this kernel's reserve) against the float64 oracle; the two forward kernels against each
@@ -3667,7 +3667,7 @@ def test_h512_fused_core_forward_route(B, T, inp, with_state, H):
     m = build_module(dict(kind="ttlstm", input_size=inp, hidden_size=H, num_layers=1, n_cores=3, tt_rank=8), dev())
     spec = m._all_layers[0]._layer_spec()
     assert F.rnn_route(spec, B, T) == "fused_core"
-    with ttrnn_hip.option("dev", 8192):
+    with ttrnn_hip.option("h512_fwd_on_tier", 1):
         assert F.rnn_route(spec, B, T) == "runtime_mfma"
     x = torch.randn(B, T, inp) * 0.5
     h0, c0 = (torch.randn(B, H) * 0.3, torch.randn(B, H) * 0.3) if with_state else (None, None)
@@ -3695,7 +3695,7 @@ def test_h512_fused_core_forward_route(B, T, inp, with_state, H):
     assert torch.equal(out[rows], part[0])
     nout = run(need_out=False)
     assert torch.equal(nout[1][0], hT) and torch.equal(nout[1][1], cT)
-    with ttrnn_hip.option("dev", 8192):
+    with ttrnn_hip.option("h512_fwd_on_tier", 1):
         g2out = run()[0]
     assert not torch.equal(g2out, out) and _maxabs(g2out, out) <= 2e-6
     # training step through this forward + the runtime tier's reverse kernel (masked loss on `rows`)
@@ -3719,7 +3719,7 @@ def test_h512_fused_core_forward_route(B, T, inp, with_state, H):
 def test_h512_fused_core_reverse_kernel(case):
     """The reference's default benchmark shape (benchmarking.py:75-83) in split mode: the reverse-time recurrence is the fused-core
     kernel on two fp16 pieces with all eight waves as gate waves (torch autograd through lstm.py:23-32,123-133 and t3nsor/ops.py:78-93
-    is what it restates); option dev bit 14 keeps the runtime tier's kernel, exact mode its own route.  Every parameter / input / initial-state
+    is what it restates); option h512_bwd_on_tier keeps the runtime tier's kernel, exact mode its own route.  Every parameter / input / initial-state
     gradient against the float64 oracle next to the runtime tier's kernel on the same inputs — output gradients over ten decades,
     steps and samples without gradient, a loss on the last step only, one core entry x 1e5, 300 samples (two rounds of
     workgroups); the kernel's own results bitwise repeatable and independent of the rest of the batch; a request for the
@@ -3777,7 +3777,7 @@ def test_h512_fused_core_reverse_kernel(case):
     got = run()
     again = run()
     sub = run([rows[2], rows[0]]) if B <= 8 else None
-    with ttrnn_hip.option("dev", 16384):
+    with ttrnn_hip.option("h512_bwd_on_tier", 1):
         assert F.rnn_backward_route(spec, B, T) == "runtime_mfma"
         tier = run()
     refs = {"x": xr.grad, "h0": h0r.grad, "c0": c0r.grad, **{n: leaves[n].grad for n, _ in m.named_parameters()}}
@@ -3808,7 +3808,7 @@ def test_h512_fused_core_reverse_kernel(case):
 @pytest.mark.parametrize("rank,inp", [(8, 1), (16, 40)])
 def test_wave_local_reverse_kernel_h256(rank, inp):
     """H = 256 launches with more samples than CUs run the reverse-time recurrence as four-wave workgroups, two per CU, whose T2 and
-    dh hand-off stay inside a wave (two barriers per step); option dev bit 15 keeps the eight-wave kernel.  Same arithmetic, another
+    dh hand-off stay inside a wave (two barriers per step); option f10bl_never keeps the eight-wave kernel.  Same arithmetic, another
     summation order in T2 (whole K per wave instead of k-block partial sums): the two agree to rounding, both meet the float64 oracle
     (autograd through lstm.py:23-32,123-133) on sampled rows; the by-products (column maxima; in = 1: the bias / input sums) come out
     of the gate threads of either kernel."""
@@ -3842,7 +3842,7 @@ def test_wave_local_reverse_kernel_h256(rank, inp):
     spec = m._all_layers[0]._layer_spec()
     assert F.rnn_backward_route(spec, B, T) == "fused_core"
     got, again = run(), run()
-    with ttrnn_hip.option("dev", 32768):
+    with ttrnn_hip.option("f10bl_never", 1):
         wide = run()
     refs = {"x": xr.grad, "h0": h0r.grad, "c0": c0r.grad, **{n: leaves[n].grad for n, _ in m.named_parameters()}}
     for n, ref in refs.items():
@@ -3930,10 +3930,10 @@ def test_runtime_reverse_kernel_ranges(meta, case):
         return got
 
     spec = m._all_layers[0]._layer_spec()
-    # (round 6: the TT-GRU of H = 512 has a fused-core reverse-time kernel of its own; option dev2 bit 8 keeps it on the tier's kernel,
+    # (round 6: the TT-GRU of H = 512 has a fused-core reverse-time kernel of its own; option gru_h512_bwd_on_tier keeps it on the tier's kernel,
     # which this test is about — the fused route runs the same cases further down)
     import contextlib
-    tier = ttrnn_hip.option("dev2", 256) if not lstm else contextlib.nullcontext()
+    tier = ttrnn_hip.option("gru_h512_bwd_on_tier", 1) if not lstm else contextlib.nullcontext()
     with tier:
         assert F.rnn_backward_route(spec, B, T) == "runtime_mfma"
         got, again = run(), run()

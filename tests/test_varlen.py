@@ -34,7 +34,7 @@ SHAPES = {
     "dense_gru": dict(kind="gru", input_size=28, hidden_size=64, num_layers=1),
 }
 # the option that moves the encoder shape from its own kernels to the other two forward kernels that take lengths
-ROUTE_OPTS = {"fused_core": None, "runtime_mfma": ("dev2", 16), "valu": ("force_generic", 1)}
+ROUTE_OPTS = {"fused_core": None, "runtime_mfma": ("enc_fwd_on_tier", 1), "valu": ("force_generic", 1)}
 
 
 @contextlib.contextmanager
@@ -85,7 +85,7 @@ def test_routes():
     m = _module("enc_lstm")
     assert _varlen_route(m, 6, 11) == "fused_core"
     assert _varlen_route(_module("enc_gru"), 6, 11) == "fused_core"
-    with ttrnn_hip.option("dev2", 16):
+    with ttrnn_hip.option("enc_fwd_on_tier", 1):
         assert _varlen_route(m, 6, 11) == "runtime_mfma"
     with ttrnn_hip.option("force_generic", 1):
         assert _varlen_route(m, 6, 11) == "valu"
@@ -241,8 +241,8 @@ TB, TT_, TLEN = 4, 9, [9, 1, 5, 8]
 TRAIN = {
     "enc_lstm": ("enc_lstm", None, ["fused_core"], TB, TT_, TLEN, True),
     "enc_gru": ("enc_gru", None, ["fused_core"], TB, TT_, TLEN, True),
-    "enc_lstm_tier_bwd": ("enc_lstm", ("dev2", 32), ["runtime_mfma"], TB, TT_, TLEN, True),
-    "enc_gru_tier_bwd": ("enc_gru", ("dev2", 32), ["runtime_mfma"], TB, TT_, TLEN, False),
+    "enc_lstm_tier_bwd": ("enc_lstm", ("enc_bwd_on_tier", 1), ["runtime_mfma"], TB, TT_, TLEN, True),
+    "enc_gru_tier_bwd": ("enc_gru", ("enc_bwd_on_tier", 1), ["runtime_mfma"], TB, TT_, TLEN, False),
     "force_generic": ("enc_lstm", ("force_generic", 1), ["valu"], TB, TT_, TLEN, True),
     "cfg2": ("cfg2", None, ["fused_core"], TB, TT_, TLEN, True),
     "gru_h256_r8": ("gru_h256_r8", None, ["fused_core"], TB, TT_, TLEN, True),

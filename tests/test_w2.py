@@ -1,8 +1,8 @@
 """The first-tier kernels of the reference's own published encoder shape — TT-LSTM hidden 768, two cores, rank 2, 40 inputs
 (experiments/speaker_verification/encoder/params_model.py:2-4,14-16; tensorized-rnn_amd/csrc/ttrnn_fast_w2.hip): forward with the
 input projection inside the recurrent kernel, reverse-time kernel with wave-local transposed stages.  Through the module API and
-the C ABI, against the oracle (float64 where operand ranges are stretched), against the runtime tier they replace (option dev2
-bits 4 / 5), and against themselves bit for bit."""
+the C ABI, against the oracle (float64 where operand ranges are stretched), against the runtime tier they replace (options
+enc_fwd_on_tier / enc_bwd_on_tier), and against themselves bit for bit."""
 import pytest
 import torch
 
@@ -24,7 +24,7 @@ def test_routes():
     torch.manual_seed(1)
     m = build_module(META, dev())
     assert _routes(m, 8, 12) == ("fused_core", "fused_core")
-    with ttrnn_hip.option("dev2", 16 | 32):
+    with ttrnn_hip.option("enc_fwd_on_tier", 1), ttrnn_hip.option("enc_bwd_on_tier", 1):
         assert _routes(m, 8, 12) == ("runtime_mfma", "runtime_mfma")
     with ttrnn_hip.fp32_math("exact"):
         assert _routes(m, 8, 12)[0] != "fused_core"
@@ -43,7 +43,7 @@ def test_routes():
     assert _routes(mg, 8, 12) == ("fused_core", "fused_core")
     assert _routes(build_module(dict(META, kind="ttgru", tt_rank=4), dev()), 8, 12) == ("fused_core", "fused_core")
     assert _routes(build_module(dict(META, kind="ttgru", tt_rank=8), dev()), 8, 12) == ("runtime_mfma", "runtime_mfma")
-    with ttrnn_hip.option("dev2", 16 | 32):
+    with ttrnn_hip.option("enc_fwd_on_tier", 1), ttrnn_hip.option("enc_bwd_on_tier", 1):
         assert _routes(mg, 8, 12) == ("runtime_mfma", "runtime_mfma")
     # ... and its four-core variants ((6, 6, 8, 8) contracted pairwise: (36, 64))
     for r in (2, 3, 4):
@@ -59,7 +59,7 @@ CASES = ["fresh", "tiny_weights", "huge_weights", "huge_h0", "zero_core", "mixed
 def test_forward_operand_ranges(case):
     """k_lstm_fwd_w2 on two fp16 pieces per operand: power-of-two scales per launch for the cores, per sample for a caller's h_0,
     per STEP for x_t (its own maximum) and for the stage hand-off.  160 steps for the fresh model, short runs for the stretched
-    operands; float64 oracle; the runtime tier (dev2 bit 4) as the second opinion; repeat launches and batch splits bit for bit."""
+    operands; float64 oracle; the runtime tier (option enc_fwd_on_tier) as the second opinion; repeat launches and batch splits bit for bit."""
     import ttrnn_hip
     torch.manual_seed(29)
     meta = dict(META, bias=False) if case == "no_bias" else META
@@ -114,7 +114,7 @@ def test_forward_operand_ranges(case):
         nost = m(xd)[0]                                              # zero initial state
         r0, _, _ = _oracle_forward("ttlstm", sd, 1, x.double())
         assert _maxabs(nost, r0) <= tol * max(1.0, float(r0.abs().max()))
-        with ttrnn_hip.option("dev2", 16):
+        with ttrnn_hip.option("enc_fwd_on_tier", 1):
             assert _routes(m, B, T)[0] == "runtime_mfma"
             tier, (_, tier_c) = m(xd, (hd, cd))
     assert torch.isfinite(out).all() and torch.isfinite(cT).all(), case
@@ -183,7 +183,7 @@ def test_training_step_vs_oracle(B, T, init, dout, rank, d):
         ref["h0"], ref["c0"] = h0r.grad, c0r.grad
     for n, r in ref.items():
         assert _maxabs(got[n], r) <= 1e-4 * max(1e-3, float(r.abs().max())), n
-    with ttrnn_hip.option("dev2", 32):
+    with ttrnn_hip.option("enc_bwd_on_tier", 1):
         _, tier = run()
     for n, r in ref.items():
         assert _maxabs(got[n], tier[n]) <= 2e-5 * max(1e-3, float(r.abs().max())), n
@@ -229,7 +229,7 @@ def test_gru_forward_operand_ranges(case):
     """k_gru_fwd_w2 (round 6): the encoder layer as a TT-GRU (speaker_encoder.py:33-47 `use_gru`; gru.py:33-44) — three waves per sample,
     four accumulator rows per unit (r, z, the hidden and the input part of n kept apart), the state image under the exponent of the
     previous step's exact maximum (a GRU's large h_0 decays only as fast as z lets it).  Same cases and yardsticks as the LSTM
-    kernel's test: float64 oracle, the runtime tier (dev2 bit 4) as the second opinion, repeat launches and batch splits bit for bit."""
+    kernel's test: float64 oracle, the runtime tier (option enc_fwd_on_tier) as the second opinion, repeat launches and batch splits bit for bit."""
     import ttrnn_hip
     torch.manual_seed(37)
     base = dict(META, kind="ttgru")
@@ -277,7 +277,7 @@ def test_gru_forward_operand_ranges(case):
         nost = m(xd)[0]
         r0 = _oracle_forward("ttgru", sd, 1, x.double())[0]
         fin = m(xd, hd, need_outputs=False) if "need_outputs" in m.forward.__code__.co_varnames else None
-        with ttrnn_hip.option("dev2", 16):
+        with ttrnn_hip.option("enc_fwd_on_tier", 1):
             assert _routes(m, B, T)[0] == "runtime_mfma"
             tier, _ = m(xd, hd)
             tier0 = m(xd)[0]
@@ -303,7 +303,7 @@ def test_gru_forward_operand_ranges(case):
 def test_gru_training_step(B, T, h0_scale, dout, rank, d):
     """k_gru_fwd_w2 + k_gru_bwd_w2 (wave-local transposed stages, three gates' hidden-chain gradients in the forward's four slots, the
     direct path dh z in registers): every gradient of a training step against the float64 oracle's autograd, and against the step
-    that runs on the tier in both directions (dev2 bits 4, 5); output gradients over ten decades, a loss on the last step only,
+    that runs on the tier in both directions (options enc_fwd_on_tier, enc_bwd_on_tier); output gradients over ten decades, a loss on the last step only,
     steps and samples without gradient; the reverse kernel's own results bit for bit on a repeat."""
     import ttrnn_hip
     from oracle import ttrnn_oracle as O
@@ -343,7 +343,7 @@ def test_gru_training_step(B, T, h0_scale, dout, rank, d):
     _, again = run()
     for n in ("x",) + (("h0",) if h0 is not None else ()):
         assert torch.equal(got[n], again[n]), n
-    with ttrnn_hip.option("dev2", 16 | 32):
+    with ttrnn_hip.option("enc_fwd_on_tier", 1), ttrnn_hip.option("enc_bwd_on_tier", 1):
         assert _routes(m, B, T) == ("runtime_mfma", "runtime_mfma")
         out_t, old = run()
     assert _maxabs(out, ro.detach()) <= (2e-3 if (h0_scale or 0) > 1 else 2e-6) * max(1.0, float(ro.abs().max()))

@@ -27,8 +27,8 @@ for cls in (TTLSTM, TTGRU):
     bi, bh = layer.input_weights.bias, layer.hidden_weights.bias
     wsb = lib.ttrnn_rnn_workspace(ctypes.byref(desc))
     res = {}
-    for name, d in (("fused", 0), ("separate", 65536)):
-        with ttrnn_hip.option("dev", d):
+    for name, on in (("fused", 0), ("separate", 1)):
+        with ttrnn_hip.option("no_fused_setup", on):
             ws = (torch.randn(wsb // 4 + 16, device=dev) if os.environ.get('GARBAGE') else torch.zeros(wsb // 4 + 16, dtype=torch.float32, device=dev))
             pin = torch.zeros(spec.in_spec.packed_elems, device=dev)
             phid = torch.zeros(spec.hid_spec.packed_elems, device=dev)

@@ -39,10 +39,10 @@ import ttrnn_hip
 NW = 8 if (os.environ.get("TTRNN_F10_NB1") == "1" or int(os.environ.get("DIAG_H", "256")) > 256) else 4      # default: the four-wave kernel k_lstm_fwd_f10q (waves 4..7: unused slots)
 if GRU or NAIVE:                             # k_gru_fwd_f10vh (ttrnn_fast_f10gh.hip) / k_rnn_fwd_f10n (ttrnn_fast_f10n.hip)
     names = ["S10 mma+gbuf", "barrier1", "gates", "S2+split", "barrier2", "-", "-", "-"]
-elif ttrnn_hip.get_fp32_math() == "split" and (int(os.environ.get("TTRNN_DEV", "0")) & 512) and RANK == 8 \
-        and os.environ.get("TTRNN_F10_NB1") != "1":      # TTRNN_DEV=512: k_lstm_fwd_f10s (ttrnn_fast_f10s.hip, A/B kernel)
+elif ttrnn_hip.get_fp32_math() == "split" and ttrnn_hip.get_option("f10s") and RANK == 8 \
+        and os.environ.get("TTRNN_F10_NB1") != "1":      # TTRNN_F10S=1: k_lstm_fwd_f10s (ttrnn_fast_f10s.hip, A/B kernel)
     names = ["S10 mma", "gates", "S2+split", "stores", "barrier", "-", "-", "-"]
-elif F.rnn_cores01_first(m._all_layers[0]._layer_spec(), B, T):      # k_lstm_fwd_f10t (ttrnn_fast_f10t.hip); TTRNN_DEV2=2048: k_lstm_fwd_f10q
+elif F.rnn_cores01_first(m._all_layers[0]._layer_spec(), B, T):      # k_lstm_fwd_f10t (ttrnn_fast_f10t.hip); TTRNN_F10T_OFF=1: k_lstm_fwd_f10q
     names = ["read+stage1", "fold+split", "stage2", "gates+stores", "barrier", "-", "-", "-"]
 elif ttrnn_hip.get_fp32_math() == "split":     # k_lstm_fwd_f10q / k_lstm_fwd_f10 (ttrnn_fast_f10q.hip, ttrnn_fast_f10.hip)
     names = ["S2+split", "barrier1", "S10 mma", "gates+stores", "barrier2", "-", "-", "-"]

@@ -45,14 +45,17 @@ int main(int argc, char** argv) {
   if (launch_gemm_half_prep(W, K, M, planes, scr, 0) != 0) { printf("prep failed\n"); return 1; }
   float best[6] = {1e9f, 1e9f, 1e9f, 1e9f, 1e9f, 1e9f};
   const char* names[6] = {"on-the-fly", "pingpong  ", "persistent", "ps nostore", "lockstep  ", "ls nostore"};
-  const int devs[6] = {0, 1, 0, 2, 64, 66};      // option `dev`: bit 0 ping-pong, bit 1 no stores, bit 6 one workgroup per tile
+  // options gemm3_pingpong / gemm3_wg_per_tile, and the ablation build's raw `dev` bit 1 (value 2): no stores
+  const struct { int pingpong, wg_per_tile, abl; } vars[6] = {{0, 0, 0}, {1, 0, 0}, {0, 0, 0}, {0, 0, 2}, {0, 1, 0}, {0, 1, 2}};
   const int NV = 6;
   // every variant runs its repetitions back to back (interleaved, a variant's time depended on what its predecessor had left
   // in the caches: a store-free predecessor made the next one 10 % faster at cfg4's size)
   for (int v = 0; v < NV; ++v)
     for (int r = 0; r < reps + 1; ++r) {
       opt_set("no_gemm3", v == 0 ? 1 : 0);
-      opt_set("dev", devs[v]);
+      opt_set("dev", vars[v].abl);
+      opt_set("gemm3_pingpong", vars[v].pingpong);
+      opt_set("gemm3_wg_per_tile", vars[v].wg_per_tile);
       CK(hipEventRecord(e0, 0));
       int st = launch_gemm_half(TTRNN_F32, rows, K, M, x, planes, scr, nullptr, M / 4, v == 0 ? y0 : y1, 0, nullptr);
       CK(hipEventRecord(e1, 0));
