@@ -76,16 +76,26 @@ class SpeakerEncoder(nn.Module):
         return ge2e.similarity_matrix(verification_embeds, self.similarity_weight.to(verification_embeds.device),
                                       self.similarity_bias.to(verification_embeds.device), enrollment_embeds)
 
-    def loss(self, verification_embeds, enrollment_embeds=None):
+    def loss(self, verification_embeds, enrollment_embeds=None, fused=None, with_eer=True):
         """(loss, eer) as speaker_encoder.py:142-170; under torch.distributed every rank passes the [S_local, U, D]
-        embeddings of its own speakers (ge2e.ge2e_loss_data_parallel: one all-gather)."""
+        embeddings of its own speakers (ge2e.ge2e_loss_data_parallel: one all-gather).  fused: True = the library's GE2E
+        kernels (ge2e.ge2e_loss_fused: four launches for loss plus gradients), False = the tensor-op path, None = the
+        kernels wherever ge2e.fused_supported says they take the call."""
         from ttrnn_hip import ge2e
         w = self.similarity_weight.to(verification_embeds.device)
         b = self.similarity_bias.to(verification_embeds.device)
+        S, U, D = verification_embeds.shape
+        if fused is None:
+            fused = ge2e.fused_supported(S, U, D, verification_embeds.dtype, verification_embeds.device,
+                                         0 if enrollment_embeds is None else enrollment_embeds.shape[1])
         if enrollment_embeds is None and torch.distributed.is_available() and torch.distributed.is_initialized() \
                 and torch.distributed.get_world_size() > 1:
-            return ge2e.ge2e_loss_data_parallel(verification_embeds, w, b)
-        return ge2e.ge2e_loss(verification_embeds, w, b, enrollment_embeds)
+            return ge2e.ge2e_loss_data_parallel(verification_embeds, w, b, with_eer=with_eer, fused=fused)
+        if fused:
+            if enrollment_embeds is not None:
+                enrollment_embeds = enrollment_embeds.detach()      # a constant (main.py:161-190): no gradient to it
+            return ge2e.ge2e_loss_fused(verification_embeds, w, b, enrollment_embeds, with_eer=with_eer)
+        return ge2e.ge2e_loss(verification_embeds, w, b, enrollment_embeds, with_eer=with_eer)
 
     def do_gradient_ops(self, clip=3.0):
         """speaker_encoder.py:60-66: scale the similarity parameters' gradients by 0.01, clip the global norm."""

@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--ttrank", type=int, default=16)
     ap.add_argument("--gru", action="store_true")
     ap.add_argument("-n", "--nruns", type=int, default=10)
+    ap.add_argument("--torch_loss", action="store_true",
+                    help="GE2E loss as torch tensor ops + autograd instead of the library's GE2E kernels (A/B)")
     args = ap.parse_args()
     dev = torch.device("cuda")
     torch.manual_seed(11)
@@ -40,8 +42,7 @@ def main():
     def step():
         opt.zero_grad(set_to_none=True)
         embeds = model(x).view(S, U, -1)
-        from ttrnn_hip import ge2e
-        loss, _ = ge2e.ge2e_loss(embeds, model.similarity_weight, model.similarity_bias, None, with_eer=False)
+        loss, _ = model.loss(embeds, fused=False if args.torch_loss else None, with_eer=False)
         loss.backward()
         model.do_gradient_ops()
         opt.step()
@@ -59,8 +60,8 @@ def main():
         embeds = model(x).view(S, U, -1)
         _, eer = model.loss(embeds)
     ms = 1e3 * sum(times) / len(times)
-    print("speaker-encoder train step: %.2f ms (min %.2f) for %d utterances x %d frames; loss %.4f, EER %.3f" % (
-        ms, 1e3 * min(times), S * U, args.frames, float(loss), eer))
+    print("speaker-encoder train step (%s GE2E loss): %.2f ms (min %.2f) for %d utterances x %d frames; loss %.4f, EER %.3f" % (
+        "torch-op" if args.torch_loss else "fused", ms, 1e3 * min(times), S * U, args.frames, float(loss), eer))
 
 
 if __name__ == "__main__":

@@ -360,6 +360,42 @@ int ttrnn_rnn_forward_varlen(const ttrnn_rnn_desc* desc, const int32_t* lengths,
 int ttrnn_rnn_varlen_seed_dout(const ttrnn_rnn_desc* desc, const int32_t* lengths, const void* d_out, const void* d_hT,
                                void* d_out_seeded, void* stream);
 
+/* ---- GE2E similarity matrix, softmax loss and gradients (additive to ABI 7: test for TTRNN_HAS_GE2E) ---------------------------
+ * The loss of the reference's speaker-verification step (experiments/speaker_verification/encoder/speaker_encoder.py:93-141
+ * similarity_matrix, :143-170 loss; main.py:65-78 the step, :161-190 validation against enrollment centroids), which the reference
+ * evaluates with a Python loop over speakers on the CPU and differentiates with torch autograd.  fp32 only.
+ *   E    fp32 [S][U][D] verification embeddings, NOT assumed normalised (the gradients carry the normalisation Jacobians);
+ *   A    fp32 [S][U_enroll][D] enrollment embeddings when desc.U_enroll > 0 (a constant: no gradient), else ignored;
+ *   w, b, g, loss  DEVICE scalars (the similarity weight / bias are nn.Parameters, speaker_encoder.py:55-56): read / written
+ *        on the device at run time, so a captured graph replays on new values.
+ * Training form (U_enroll == 0, U >= 2), with normalize(x) = x / max(|x|, 1e-12):
+ *   c_s = sum_u E[s,u];  incl_j = normalize(c_j / U);  excl_su = normalize((c_s - E[s,u]) / (U - 1))
+ *   sim[s,u,j] = E[s,u] . incl_j (j != s),  sim[s,u,s] = E[s,u] . excl_su                      (speaker_encoder.py:109-124)
+ * Enrollment form: sim[s,u,j] = E[s,u] . normalize(mean_u A[j,u])                                (speaker_encoder.py:125-130)
+ * Both: out = w sim + b;  loss = mean over the S U rows of cross_entropy(out[row,:], s), softmax max-subtracted (:154-159).
+ * ttrnn_ge2e_forward   writes loss (NULL-able) and, when sim_out != NULL, out[S][U][S] (what the host-side EER reads, :161-169).
+ *                      need_grad != 0 leaves in the workspace what ttrnn_ge2e_backward reads; three launches (centroids, rows,
+ *                      centroid gradients + the loss's final sum).
+ * ttrnn_ge2e_backward  one launch: d_E[S][U][D], d_w, d_b (each NULL-able) for the upstream gradient *g (NULL = 1).  It reads
+ *                      the workspace the forward left and may be called repeatedly; after a forward with need_grad == 0 the
+ *                      results are NaN.  E and w are the forward's.
+ * Every sum across workgroups goes through per-workgroup partials added in a fixed order: no atomics, results repeatable bit
+ * for bit.  No allocation, no synchronisation, capture-safe; workspace of ttrnn_ge2e_workspace(desc) bytes (0 for a descriptor
+ * the calls refuse).  TTRNN_ERR_BAD_DESC: non-positive sizes, U < 2 in the training form; TTRNN_ERR_UNSUPPORTED: S > 2048,
+ * D > 4096 or more than 2^22 rows. */
+#define TTRNN_HAS_GE2E 1
+typedef struct ttrnn_ge2e_desc {
+  int32_t S;             /* speakers                                                            */
+  int32_t U;             /* verification utterances per speaker                                 */
+  int32_t D;             /* embedding size                                                      */
+  int32_t U_enroll;      /* 0 = training form; > 0: enrollment utterances per speaker           */
+} ttrnn_ge2e_desc;
+size_t ttrnn_ge2e_workspace(const ttrnn_ge2e_desc* desc);
+int ttrnn_ge2e_forward(const ttrnn_ge2e_desc* desc, const float* E, const float* A, const float* w, const float* b, float* loss,
+                       float* sim_out, int need_grad, void* workspace, size_t workspace_bytes, void* stream);
+int ttrnn_ge2e_backward(const ttrnn_ge2e_desc* desc, const float* E, const float* w, const float* g, float* d_E, float* d_w,
+                        float* d_b, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Reverse-time part of BPTT (reference: torch autograd through lstm.py:123-133 / gru.py:124-134).
  *   d_out[B][T][H], d_hT/d_cT[B][H] (any may be NULL = zeros)
  *   -> d_gates_in[B][T][G*H], d_gates_hid[B][T][G*H] (fp32: gradients w.r.t. the outputs of the

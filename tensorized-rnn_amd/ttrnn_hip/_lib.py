@@ -52,6 +52,11 @@ class LinHints(ctypes.Structure):
                 ("x_period", ctypes.c_int64), ("x_first", ctypes.c_void_p), ("dy_rowmax", ctypes.c_void_p)]
 
 
+class Ge2eDesc(ctypes.Structure):
+    """struct ttrnn_ge2e_desc (include/ttrnn.h, TTRNN_HAS_GE2E)"""
+    _fields_ = [("S", ctypes.c_int32), ("U", ctypes.c_int32), ("D", ctypes.c_int32), ("U_enroll", ctypes.c_int32)]
+
+
 _P = ctypes.c_void_p
 _SIGNATURES = {
     "ttrnn_abi_version": (ctypes.c_int, []),
@@ -103,6 +108,10 @@ _SIGNATURES = {
     "ttrnn_rnn_varlen_workspace": (ctypes.c_size_t, [ctypes.POINTER(RnnDesc)]),
     "ttrnn_rnn_forward_varlen": (ctypes.c_int, [ctypes.POINTER(RnnDesc)] + [_P] * 13 + [ctypes.c_size_t, _P]),
     "ttrnn_rnn_varlen_seed_dout": (ctypes.c_int, [ctypes.POINTER(RnnDesc), _P, _P, _P, _P, _P]),
+    # GE2E similarity / loss / gradients (TTRNN_HAS_GE2E)
+    "ttrnn_ge2e_workspace": (ctypes.c_size_t, [ctypes.POINTER(Ge2eDesc)]),
+    "ttrnn_ge2e_forward": (ctypes.c_int, [ctypes.POINTER(Ge2eDesc), _P, _P, _P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "ttrnn_ge2e_backward": (ctypes.c_int, [ctypes.POINTER(Ge2eDesc), _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "ttrnn_rnn_backward_workspace": (ctypes.c_size_t, [ctypes.POINTER(RnnDesc)]),
     "ttrnn_rnn_backward_workspace_ex": (ctypes.c_size_t, [ctypes.POINTER(RnnDesc), ctypes.c_int]),
     "ttrnn_rnn_backward_route": (ctypes.c_int, [ctypes.POINTER(RnnDesc), ctypes.c_int]),

@@ -6,9 +6,15 @@ first).  Here the whole thing is a handful of device-side tensor ops — inclusi
 diagonal, one [S*U, D] x [D, S] product — so it stays on the GPU next to the encoder, and under data parallelism every
 rank contributes its utterances through one all-gather of the [S_local, U, D] embeddings (gradients flow back to the
 local slice only; the loss is the mean over ALL utterances, as on a single device)."""
+import contextlib
+import ctypes
+import functools
+
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+from . import _lib
 
 
 def similarity_matrix(verification, weight, bias, enrollment=None):
@@ -70,19 +76,152 @@ class _GatherSpeakers(torch.autograd.Function):
         return grad[ctx.rank * ctx.n:(ctx.rank + 1) * ctx.n].contiguous() * ctx.world, None
 
 
-def ge2e_loss_data_parallel(local_embeds, weight, bias, group=None, with_eer=False, force_gather=False):
+# ---- the same loss as library calls (include/ttrnn.h, TTRNN_HAS_GE2E): centroids, rows, centroid gradients, d_E ----------------
+
+def _desc(S, U, D, U_enroll=0):
+    d = _lib.Ge2eDesc()
+    d.S, d.U, d.D, d.U_enroll = int(S), int(U), int(D), int(U_enroll)
+    return d
+
+
+def fused_supported(S, U, D, dtype, device, U_enroll=0):
+    """True when ge2e_loss_fused / similarity_matrix_fused take this call: fp32 embeddings on a GPU and a shape the kernels
+    accept (training form U >= 2; S <= 2048, D <= 4096, at most 2^22 rows)."""
+    if dtype != torch.float32 or torch.device(device).type != "cuda":
+        return False
+    return _plan(int(S), int(U), int(D), int(U_enroll))[1] > 0
+
+
+@functools.lru_cache(maxsize=64)
+def _plan(S, U, D, U_enroll):
+    """(descriptor, workspace bytes; 0 = refused) of one shape — pure host arithmetic in the library, cached per shape."""
+    desc = _desc(S, U, D, U_enroll)
+    return desc, int(_lib.load().ttrnn_ge2e_workspace(ctypes.byref(desc)))
+
+
+def _on(device):
+    """The launches go to the CURRENT device's copy of the kernels: switch only when the tensors live elsewhere."""
+    return contextlib.nullcontext() if torch.cuda.current_device() == device.index else torch.cuda.device(device)
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def _stream(t):
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _scalar(name, t, like):
+    if not torch.is_tensor(t) or t.numel() != 1:
+        raise _lib.TtrnnError("{} must be a one-element tensor (the kernels read it on the device)".format(name))
+    if t.device != like.device or t.dtype != torch.float32:
+        raise _lib.TtrnnError("{} is {} on {}: the fused GE2E loss needs float32 on {}".format(name, t.dtype, t.device, like.device))
+    return t.detach().contiguous()
+
+
+def _fused_operands(verification, weight, bias, enrollment):
+    if verification.dim() != 3:
+        raise _lib.TtrnnError("verification embeddings must be [S, U, D], got {}".format(tuple(verification.shape)))
+    S, U, D = verification.shape
+    if not verification.is_cuda or verification.dtype != torch.float32:
+        raise _lib.TtrnnError("the fused GE2E loss runs on float32 GPU tensors only (got {} on {}); there is no fallback — "
+                              "call ge2e_loss for the tensor-op path".format(verification.dtype, verification.device))
+    Ue = 0
+    if enrollment is not None:
+        if (enrollment.dim() != 3 or enrollment.shape[0] != S or enrollment.shape[2] != D or enrollment.shape[1] < 1
+                or enrollment.device != verification.device or enrollment.dtype != torch.float32):
+            raise _lib.TtrnnError("enrollment embeddings must be float32 [S, U_enroll, D] on the verification embeddings' device")
+        Ue = enrollment.shape[1]
+    desc, nbytes = _plan(S, U, D, Ue)
+    if nbytes == 0:
+        raise _lib.TtrnnError("the fused GE2E kernels do not take S={} U={} D={} U_enroll={}".format(S, U, D, Ue))
+    E = verification.detach().contiguous()
+    A = enrollment.detach().contiguous() if enrollment is not None else None
+    return desc, nbytes, E, A, _scalar("weight", weight, E), _scalar("bias", bias, E)
+
+
+def _fused_forward(verification, weight, bias, enrollment=None, want_sim=False, need_grad=False, workspace=None):
+    """ttrnn_ge2e_forward on torch tensors -> (loss [], sim [S, U, S] or None, state for _fused_backward).  `workspace`: a uint8
+    tensor of at least ttrnn_ge2e_workspace bytes to use instead of a fresh one (its contents do not matter)."""
+    desc, nbytes, E, A, w, b = _fused_operands(verification, weight, bias, enrollment)
+    S, U, _ = E.shape
+    with _on(E.device):
+        ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=E.device)
+        loss = torch.empty((), dtype=torch.float32, device=E.device)
+        sim = torch.empty((S, U, S), dtype=torch.float32, device=E.device) if want_sim else None
+        _lib.check(_lib.load().ttrnn_ge2e_forward(ctypes.byref(desc), _ptr(E), _ptr(A), _ptr(w), _ptr(b), _ptr(loss), _ptr(sim),
+                                                  1 if need_grad else 0, _ptr(ws), ws.numel(), _stream(E)), "ttrnn_ge2e_forward")
+    return loss, sim, (desc, E, w, ws)
+
+
+def _fused_backward(state, grad=None, want=(True, True, True)):
+    """ttrnn_ge2e_backward -> (d_E, d_w, d_b), None where not wanted; grad: upstream gradient of the loss (device scalar) or None = 1."""
+    desc, E, w, ws = state
+    with _on(E.device):
+        g = grad.detach().to(torch.float32).contiguous() if grad is not None else None
+        d_E = torch.empty_like(E) if want[0] else None
+        d_w = torch.empty((), dtype=torch.float32, device=E.device) if want[1] else None
+        d_b = torch.empty((), dtype=torch.float32, device=E.device) if want[2] else None
+        _lib.check(_lib.load().ttrnn_ge2e_backward(ctypes.byref(desc), _ptr(E), _ptr(w), _ptr(g), _ptr(d_E), _ptr(d_w), _ptr(d_b),
+                                                   _ptr(ws), ws.numel(), _stream(E)), "ttrnn_ge2e_backward")
+    return d_E, d_w, d_b
+
+
+class _FusedGE2E(torch.autograd.Function):
+    """loss (and the scaled similarity matrix, not differentiable) from ttrnn_ge2e_forward; backward = ttrnn_ge2e_backward."""
+
+    @staticmethod
+    def forward(ctx, verification, weight, bias, enrollment, want_sim):
+        need = any(ctx.needs_input_grad[:3])
+        loss, sim, state = _fused_forward(verification, weight, bias, enrollment, want_sim, need)
+        ctx.state, ctx.need = state, need
+        ctx.w_shape, ctx.b_shape = weight.shape, bias.shape
+        if sim is None:
+            return loss
+        ctx.mark_non_differentiable(sim)
+        return loss, sim
+
+    @staticmethod
+    def backward(ctx, grad_loss, *unused):
+        want = tuple(ctx.needs_input_grad[:3])
+        d_E, d_w, d_b = _fused_backward(ctx.state, grad_loss, want)
+        return (d_E, d_w.reshape(ctx.w_shape) if d_w is not None else None,
+                d_b.reshape(ctx.b_shape) if d_b is not None else None, None, None)
+
+
+def similarity_matrix_fused(verification, weight, bias, enrollment=None):
+    """similarity_matrix as one library call (forward only; the inputs are treated as detached) -> [S, U, S]."""
+    return _fused_forward(verification, weight, bias, enrollment, want_sim=True, need_grad=False)[1]
+
+
+def ge2e_loss_fused(verification, weight, bias, enrollment=None, with_eer=False):
+    """ge2e_loss through the library's GE2E kernels: (loss, EER or None).  Gradients reach verification, weight and bias (four
+    launches for loss plus all gradients); the enrollment embeddings are a constant.  Raises TtrnnError on CPU tensors,
+    non-fp32 or shapes the kernels refuse — there is no fallback to the tensor-op path."""
+    if enrollment is not None and enrollment.requires_grad:
+        raise _lib.TtrnnError("the fused GE2E loss has no gradient to the enrollment embeddings (detach them)")
+    S, U, _ = verification.shape
+    if not with_eer:
+        return _FusedGE2E.apply(verification, weight, bias, enrollment, False), None
+    loss, sim = _FusedGE2E.apply(verification, weight, bias, enrollment, True)
+    return loss, eer(sim.reshape(S * U, S).cpu().numpy(), S, U)
+
+
+def ge2e_loss_data_parallel(local_embeds, weight, bias, group=None, with_eer=False, force_gather=False, fused=False):
     """Every rank holds [S_local, U, D] embeddings of its own speakers.  The similarity matrix needs all centroids: one
     all-gather (cfg4: 512 x 256 floats), then each rank evaluates the FULL loss (identical on every rank, returned
     unscaled) and back-propagates into its slice.  After the gradient all-reduce (MEAN) of the data-parallel step
     (ttrnn_hip.dist.FlatGradAllReduce) every parameter holds its single-device gradient: the slice gradient is scaled by
     the world size in _GatherSpeakers.backward, the replicated similarity weight / bias are left alone.
-    (The reference computes the loss on one CPU, main.py:280.)"""
+    (The reference computes the loss on one CPU, main.py:280.)  fused=True: the full loss after the gather is ge2e_loss_fused."""
     import os
     import torch.distributed as dist
+    loss_fn = ge2e_loss_fused if fused else ge2e_loss
     if not (dist.is_available() and dist.is_initialized()):
-        return ge2e_loss(local_embeds, weight, bias, None, with_eer)
+        return loss_fn(local_embeds, weight, bias, None, with_eer)
     # force_gather / TTRNN_FORCE_COLLECTIVES=1: take the all-gather even in a one-rank group (drives RCCL on a 1-GPU box)
     if dist.get_world_size(group) == 1 and not (force_gather or os.environ.get("TTRNN_FORCE_COLLECTIVES") == "1"):
-        return ge2e_loss(local_embeds, weight, bias, None, with_eer)
+        return loss_fn(local_embeds, weight, bias, None, with_eer)
     full = _GatherSpeakers.apply(local_embeds, group)
-    return ge2e_loss(full, weight, bias, None, with_eer)
+    return loss_fn(full, weight, bias, None, with_eer)
