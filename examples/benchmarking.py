@@ -18,7 +18,9 @@ from models import MNISTClassifier
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--tt", action="store_true")
+    ap.add_argument("--tt", action="store_true", help="accepted and ignored: the TT model is the default")
+    ap.add_argument("--dense", action="store_true",
+                    help="the uncompressed baseline (the reference's tt=False): dense LSTM / GRU + nn.Linear")
     ap.add_argument("--ncores", type=int, default=3)
     ap.add_argument("--ttrank", type=int, default=8)
     ap.add_argument("--batch_size", type=int, default=512)
@@ -37,7 +39,7 @@ def main():
     device = torch.device("cuda")
     with contextlib.redirect_stdout(io.StringIO()):
         model = MNISTClassifier(args.in_size, args.emb_size, args.hidden_size, args.n_layers, device, gru=args.gru,
-                                n_cores=args.ncores, tt_rank=args.ttrank, naive_tt=args.naive_tt).to(device)
+                                n_cores=args.ncores, tt_rank=args.ttrank, naive_tt=args.naive_tt, tt=not args.dense).to(device)
     data = torch.from_numpy(np.random.rand(args.batch_size, args.seq_len, args.in_size).astype("float32")).to(device)
     target = torch.from_numpy(np.random.randint(0, args.emb_size, args.batch_size).astype("int64")).to(device)
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
@@ -64,12 +66,21 @@ def main():
     durations = []
     for _ in range(args.nruns):
         t0 = time.perf_counter()
-        step()
+        last = step()
         torch.cuda.synchronize()
         durations.append(time.perf_counter() - t0)
     d = np.array(durations)
     print("mean time: {:.6f} s \t std time: {:.6f} s \t timesteps/s: {:.0f}".format(d.mean(), d.std(), args.seq_len / d.mean()))
     print("model has: {} parameters".format(model.param_count()))
+    if args.dense:
+        from ttrnn_hip import functional as TF
+        spec = model.rnn.cell0._layer_spec()
+        print("recurrent kernels: forward {}, reverse {}".format(TF.rnn_route(spec, args.batch_size, args.seq_len),
+                                                                 TF.rnn_backward_route(spec, args.batch_size, args.seq_len)))
+        if args.train:
+            print("loss: {:.6f}".format(float(last)))                 # of the last timed step
+        else:
+            print("max log-probability: {:.6f}".format(float(last.max())))      # of the last timed forward
 
 
 if __name__ == "__main__":

@@ -19,15 +19,23 @@ import torch.nn.functional as F  # noqa: E402
 from torch import nn  # noqa: E402
 
 from t3nsor.layers import TTLinear  # noqa: E402
-from tensorized_rnn.gru import TTGRU  # noqa: E402
+from tensorized_rnn.gru import GRU, TTGRU  # noqa: E402
+from tensorized_rnn.lstm import LSTM  # noqa: E402
 from tensorized_rnn.tt_lstm import TTLSTM  # noqa: E402
 
 
 class MNISTClassifier(nn.Module):
     def __init__(self, input_size, output_size, hidden_size, num_layers, device, gru=False, n_cores=3, tt_rank=8,
-                 naive_tt=False, extra_core=None, log_grads=False):
+                 naive_tt=False, extra_core=None, log_grads=False, tt=True):
         super().__init__()
         self.gru = gru
+        self.tt = tt
+        if not tt:
+            # the uncompressed baseline (mnist_classifier.py:36-45): dense LSTM / GRU + nn.Linear
+            self.rnn = (GRU if gru else LSTM)(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
+                                              device=device, log_grads=log_grads)
+            self.linear = nn.Linear(hidden_size, output_size).to(device)
+            return
         cls = TTGRU if gru else TTLSTM
         self.rnn = cls(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers, device=device,
                        n_cores=n_cores, tt_rank=tt_rank, log_grads=log_grads, is_naive=naive_tt, new_core=extra_core)
@@ -44,18 +52,28 @@ class MNISTClassifier(nn.Module):
         # (inference: the [B, T, H] outputs of the last layer are not even written — need_outputs=False)
         res = self.rnn(inputs) if torch.is_grad_enabled() else self.rnn(inputs, need_outputs=False)
         last = res[1] if self.gru else res[1][0]
+        if not self.tt:
+            return F.log_softmax(self.linear(last), dim=1)                  # mnist_classifier.py:55-57
         return self.linear.forward_head(last, "log_softmax")                # TTLinear + log_softmax: one library call
 
 
 class SpeakerEncoder(nn.Module):
     def __init__(self, mel_n_channels, hidden_size, num_layers, embedding_size, device, n_cores=3, rank=16,
-                 use_gru=False):
+                 use_gru=False, compression='tt'):
         super().__init__()
-        cls = TTGRU if use_gru else TTLSTM
         self.use_gru = use_gru
-        self.rnn = cls(mel_n_channels, hidden_size, num_layers, device, n_cores=n_cores, tt_rank=rank)
-        self.linear = TTLinear(in_features=hidden_size, out_features=embedding_size, bias=True, auto_shapes=True,
-                               d=n_cores, tt_rank=rank).to(device)
+        self.compression = compression
+        if compression is None:
+            # the uncompressed baseline (speaker_encoder.py:28-38): dense LSTM / GRU stack + nn.Linear
+            self.rnn = (GRU if use_gru else LSTM)(mel_n_channels, hidden_size, num_layers, device)
+            self.linear = nn.Linear(in_features=hidden_size, out_features=embedding_size).to(device)
+        elif compression == 'tt':
+            cls = TTGRU if use_gru else TTLSTM
+            self.rnn = cls(mel_n_channels, hidden_size, num_layers, device, n_cores=n_cores, tt_rank=rank)
+            self.linear = TTLinear(in_features=hidden_size, out_features=embedding_size, bias=True, auto_shapes=True,
+                                   d=n_cores, tt_rank=rank).to(device)
+        else:
+            raise ValueError("Unknown compression type: '{}'".format(compression))
         self.similarity_weight = nn.Parameter(torch.tensor([10.]))
         self.similarity_bias = nn.Parameter(torch.tensor([-5.]))
 
@@ -68,6 +86,9 @@ class SpeakerEncoder(nn.Module):
         else:
             res = self.rnn(utterances) if torch.is_grad_enabled() else self.rnn(utterances, need_outputs=False)
         last_hidden = res[1] if self.use_gru else res[1][0]
+        if self.compression is None:
+            embeds_raw = torch.relu(self.linear(last_hidden))                    # speaker_encoder.py:86-89
+            return embeds_raw / torch.norm(embeds_raw, dim=1, keepdim=True)
         return self.linear.forward_head(last_hidden, "relu_l2norm")              # TTLinear + ReLU + L2 norm: one library call
 
     def similarity_matrix(self, verification_embeds, enrollment_embeds=None):

@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--ncores", type=int, default=3)
     ap.add_argument("--ttrank", type=int, default=16)
     ap.add_argument("--gru", action="store_true")
+    ap.add_argument("--dense", action="store_true",
+                    help="the uncompressed baseline (the reference's compression=None): dense LSTM / GRU stack + nn.Linear")
     ap.add_argument("-n", "--nruns", type=int, default=10)
     ap.add_argument("--torch_loss", action="store_true",
                     help="GE2E loss as torch tensor ops + autograd instead of the library's GE2E kernels (A/B)")
@@ -34,7 +36,7 @@ def main():
     torch.manual_seed(11)
     with contextlib.redirect_stdout(io.StringIO()):
         model = SpeakerEncoder(args.mels, args.hidden_size, args.n_layers, args.emb_size, dev, n_cores=args.ncores,
-                               rank=args.ttrank, use_gru=args.gru).to(dev)
+                               rank=args.ttrank, use_gru=args.gru, compression=None if args.dense else 'tt').to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     S, U = args.speakers, args.utterances
     x = torch.rand(S * U, args.frames, args.mels, device=dev)
@@ -62,6 +64,11 @@ def main():
     ms = 1e3 * sum(times) / len(times)
     print("speaker-encoder train step (%s GE2E loss): %.2f ms (min %.2f) for %d utterances x %d frames; loss %.4f, EER %.3f" % (
         "torch-op" if args.torch_loss else "fused", ms, 1e3 * min(times), S * U, args.frames, float(loss), eer))
+    if args.dense:
+        from ttrnn_hip import functional as TF
+        spec = model.rnn.cell0._layer_spec()
+        print("recurrent kernels: forward {}, reverse {}".format(TF.rnn_route(spec, S * U, args.frames),
+                                                                 TF.rnn_backward_route(spec, S * U, args.frames)))
 
 
 if __name__ == "__main__":

@@ -309,6 +309,23 @@ int ttrnn_rnn_forward_cores(const ttrnn_rnn_desc* desc, const void* x, const voi
 #define TTRNN_ROUTE_FUSED_CORE 2      /* shape-specialised fused-core kernels (ttrnn_fast_f10*.hip)                    */
 #define TTRNN_ROUTE_MERGED_BIG 3      /* merged two-core kernels of the H = 1024, d = 4, r = 32 shape (ttrnn_fast_big) */
 #define TTRNN_ROUTE_RUNTIME_MFMA 4    /* runtime-shape two-stage MFMA kernels, any d >= 2 (ttrnn_g2.hip)               */
+/* Additive to ABI 7 (test for TTRNN_HAS_DENSE_ROUTE): the reference's uncompressed baselines — tensorized_rnn/lstm.py:7-41 /
+ * gru.py:9-50, nn.Linear weights presented as d = 1 TT-matrices — as one MFMA GEMM launch per time step,
+ * [x_t | h_{t-1}] . [W_in ; W_hh] on three bf16 pieces per operand with the cell arithmetic as the epilogue
+ * (ttrnn_fast_dense.hip).  Taken for in_w.d == hid_w.d == 1, fp32 storage, TTRNN_MATH_SPLIT, hid_blocks <= 1, hidden_size >= 128
+ * and a multiple of 32, any input_size, batch and seq_len >= 1; the reverse-time part the same way, last step first
+ * (ttrnn_rnn_backward_stats = 0).  A forward with lengths (ttrnn_rnn_forward_varlen*) and d_state requests keep their routes; the
+ * REVERSE of a call with lengths does take this route (ttrnn_rnn_backward_ex cannot see lengths: it runs unchanged on the frozen
+ * records, as every reverse family does).  Option force_generic is the A/B switch back to the any-shape kernels.  Launches per
+ * call: seq_len + 1 forward, seq_len + 2 reverse; results are repeatable bit for bit and a sample's result does not depend on the
+ * batch it runs in.  Workspaces (bytes; Bp = batch rounded up to 32,
+ * Kxp = input_size rounded up to 32, G = 4 LSTM / 3 GRU):
+ *   ttrnn_rnn_workspace            24 (Kxp + H) H + 24 Bp H
+ *   ttrnn_rnn_backward_workspace_ex(desc, 0)   6 G H H + 12 Bp G H + 4 Bp H
+ * (one formula for both cells: the forward's includes the c buffer a GRU does not use, the fp32 h ping-pong only a GRU's
+ * out == NULL call uses, and the GRU's two all-zero half-slots of the weight planes, which the kernel skips) */
+#define TTRNN_ROUTE_DENSE_STEP 5
+#define TTRNN_HAS_DENSE_ROUTE 1
 int ttrnn_rnn_forward_route(const ttrnn_rnn_desc* desc);   /* TTRNN_ROUTE_* or a negative ttrnn_status */
 /* Samples one workgroup of the recurrent forward kernel carries (1, or 2: the runtime-shape tier pairs samples where the hidden
  * matrix's merged head is streamed from L2 every step and the batch exceeds the CU count, so that each streamed block feeds two —

@@ -161,6 +161,9 @@ bool resident_at_once(const void* fn, int block_threads, size_t dyn_lds, long bl
 static bool force_generic() { return opt(OPT_FORCE_GENERIC) != 0; }
 static bool no_gemm() { return opt(OPT_NO_GEMM) != 0; }
 static int fp32_math() { return opt(OPT_FP32_MATH); }
+// the dense (d = 1) step kernels of ttrnn_fast_dense.hip take this descriptor (route TTRNN_ROUTE_DENSE_STEP)?  No other family
+// takes d = 1 matrices, so the test stands in front of every other route's; calls with lengths or a d_state request never ask
+static bool dense_step(const RnnShape& rs, int dtype) { return !force_generic() && dense_step_available(rs, dtype, fp32_math()); }
 
 extern "C" {
 
@@ -613,6 +616,7 @@ static size_t rnn_workspace_other(const RnnShape& rs, int dtype);
 size_t ttrnn_rnn_workspace(const ttrnn_rnn_desc* desc) {
   RnnShape rs;
   if (rnn_shape_init(&rs, desc) != TTRNN_OK) return 0;
+  if (dense_step(rs, desc->dtype)) return dense_step_fwd_workspace(rs);
   // (the encoder-shape kernel's fragments, or whatever the route behind it needs: an option may switch between calls)
   const size_t w2 = w2_rnn_fwd_available(rs, desc->dtype) ? w2_rnn_fwd_workspace_bytes() : 0;
   const size_t o = rnn_workspace_other(rs, desc->dtype);
@@ -635,6 +639,7 @@ size_t ttrnn_rnn_backward_workspace_ex(const ttrnn_rnn_desc* desc, int want_stat
   // the same decisions, in the same order, as ttrnn_rnn_backward_ex: a d_state request takes the runtime-shape / any-shape
   // route whatever the shape, and only then is their (per-sample, much larger) plan part of the answer
   const bool gen = force_generic();
+  if (!want_state && dense_step(rs, desc->dtype)) return dense_step_bwd_workspace(rs);
   if (!want_state && !gen && rs.T > 0 && w2_rnn_bwd_available(rs, desc->dtype)) return w2_rnn_bwd_workspace_bytes();
   const bool g2_first = (opt(OPT_FORCE_G2) || want_state) && !gen && rs.T > 0 && g2_rnn_bwd_available(rs, desc->dtype);
   if (!g2_first && !want_state && !gen && fast_rnn_bwd_available(rs, desc->dtype)) {
@@ -717,6 +722,12 @@ int ttrnn_rnn_forward_phase(const ttrnn_rnn_desc* desc, int phase, const void* x
     return TTRNN_ERR_NULL;
   if (rs.has_bias_in && !bias_in) return TTRNN_ERR_NULL;
   if (rs.has_bias_hid && !bias_hid) return TTRNN_ERR_NULL;
+  if (dense_step(rs, desc->dtype)) {
+    // the uncompressed baselines: one GEMM launch per time step, the cell as its epilogue (no weight-only phase to separate)
+    if (!workspace || workspace_bytes < dense_step_fwd_workspace(rs)) return TTRNN_ERR_WORKSPACE;
+    return launch_rnn_fwd_dense(rs, x, h0, c0, packed_in, bias_in, packed_hid, bias_hid, out, hT, cT, reserve, workspace,
+                                (hipStream_t)stream);
+  }
   if (rs.T > 0 && w2_rnn_fwd_available(rs, desc->dtype)) {
     // the speaker encoder's shape: chain stages AND input projection in one persistent kernel (no K-in, no [B][T][4H] buffer)
     if (!workspace || workspace_bytes < w2_rnn_fwd_workspace_bytes()) return TTRNN_ERR_WORKSPACE;
@@ -856,6 +867,7 @@ int ttrnn_rnn_forward_route(const ttrnn_rnn_desc* desc) {
   RnnShape rs;
   if (rnn_shape_init(&rs, desc) != TTRNN_OK) return TTRNN_ERR_BAD_DESC;
   if (force_generic()) return TTRNN_ROUTE_VALU;
+  if (dense_step(rs, desc->dtype)) return TTRNN_ROUTE_DENSE_STEP;
   if (w2_rnn_fwd_available(rs, desc->dtype)) return TTRNN_ROUTE_FUSED_CORE;
   if (fwd_prefers_g2(rs, desc->dtype))      // (the fp32 GRU shape with input_size != 1: the tier's K-in + the fused-core recurrent kernel)
     return (!opt(OPT_FORCE_G2) && (f10gh_available(rs, desc->dtype) || f10g5_available(rs, desc->dtype) || f10n_available(rs, desc->dtype))) ? TTRNN_ROUTE_FUSED_CORE
@@ -964,6 +976,7 @@ int ttrnn_rnn_backward_route(const ttrnn_rnn_desc* desc, int want_state) {
   RnnShape rs;
   if (rnn_shape_init(&rs, desc) != TTRNN_OK) return TTRNN_ERR_BAD_DESC;
   if (force_generic()) return TTRNN_ROUTE_VALU;
+  if (!want_state && dense_step(rs, desc->dtype)) return TTRNN_ROUTE_DENSE_STEP;
   if (!want_state && rs.T > 0 && w2_rnn_bwd_available(rs, desc->dtype)) return TTRNN_ROUTE_FUSED_CORE;
   const bool g2_first = (opt(OPT_FORCE_G2) || want_state) && rs.T > 0 && g2_rnn_bwd_available(rs, desc->dtype);
   if (!g2_first && !want_state && fast_rnn_bwd_available(rs, desc->dtype)) {
@@ -984,6 +997,7 @@ int ttrnn_rnn_backward_route(const ttrnn_rnn_desc* desc, int want_state) {
 // the column maxima, and the input_size == 1 sums; the merged-big kernels: the column maxima
 static int bwd_stats_mask(const RnnShape& rs, int dtype) {
   if (force_generic() || opt(OPT_FORCE_G2) || rs.T < 1 || rs.B < 1) return 0;
+  if (dense_step(rs, dtype)) return 0;      // (by-product statistics from the step kernels: not built)
   if (w2_rnn_bwd_available(rs, dtype)) return TTRNN_BWD_STATS_COLMAX;
   if (fast_rnn_bwd_available(rs, dtype) && (fp32_math() == TTRNN_MATH_SPLIT || dtype == TTRNN_BF16) &&
       f10_rnn_bwd_available(rs, dtype))
@@ -1031,6 +1045,12 @@ int ttrnn_rnn_backward_ex(const ttrnn_rnn_desc* desc, const void* out, const voi
   // reverse kernels; a request for it takes those routes (the shape-specialised kernels stay untouched)
   const bool g2_first = (opt(OPT_FORCE_G2) || d_state) && !force_generic() && rs.T > 0 && g2_rnn_bwd_available(rs, desc->dtype);
   const bool want_state = d_state != nullptr;
+  if (!want_state && dense_step(rs, desc->dtype)) {
+    // the uncompressed baselines: one launch per step, last step first, and a closing launch for d_h0 / d_c0
+    if (!workspace || workspace_bytes < dense_step_bwd_workspace(rs)) return TTRNN_ERR_WORKSPACE;
+    return launch_rnn_bwd_dense(rs, out, h0, c0, packed_hid, reserve, d_out, d_hT, d_cT, d_gates_in, d_gates_hid, d_h0, d_c0,
+                                workspace, (hipStream_t)stream);
+  }
   if (!want_state && !force_generic() && rs.T > 0 && w2_rnn_bwd_available(rs, desc->dtype)) {
     // the speaker encoder's shape: wave-local transposed stages, one barrier per step (ttrnn_fast_w2.hip)
     if (!workspace || workspace_bytes < w2_rnn_bwd_workspace_bytes()) return TTRNN_ERR_WORKSPACE;

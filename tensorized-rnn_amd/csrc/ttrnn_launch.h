@@ -412,6 +412,18 @@ int launch_rnn_bwd_w2(const RnnShape& rs, const void* out, const void* h0, const
                       const void* d_out, const void* d_hT, const void* d_cT, float* dg_in, float* dg_hid, void* d_h0, void* d_c0, void* ws,
                       hipStream_t stream, float* stats = nullptr);
 
+// dense (d = 1, nn.Linear) LSTM / GRU layers as one MFMA GEMM launch per time step with the cell as its epilogue
+// (ttrnn_fast_dense.hip, plan: ttrnn_dense.h): fp32 storage, split math, H >= 128 and a multiple of 32, any input_size
+bool dense_step_available(const RnnShape& rs, int dtype, int fp32_math);
+size_t dense_step_fwd_workspace(const RnnShape& rs);
+size_t dense_step_bwd_workspace(const RnnShape& rs);
+int launch_rnn_fwd_dense(const RnnShape& rs, const void* x, const void* h0, const void* c0, const float* packed_in,
+                         const void* bias_in, const float* packed_hid, const void* bias_hid, void* out, void* hT, void* cT,
+                         float* reserve, void* ws, hipStream_t stream);
+int launch_rnn_bwd_dense(const RnnShape& rs, const void* out, const void* h0, const void* c0, const float* packed_hid,
+                         const float* reserve, const void* d_out, const void* d_hT, const void* d_cT, float* dg_in, float* dg_hid,
+                         void* d_h0, void* d_c0, void* ws, hipStream_t stream);
+
 // chain weight gradients of up to two TT-matrices sharing one pass over dy (ttrnn_fast_c2w.hip, plan: ttrnn_c2w.h)
 bool c2w_prefers_chain(const TtShape& s);      // 2 in out > 1.5 x the chain's FLOPs
 size_t c2w_workspace_bytes(const TtShape* const* shapes, int nmat, bool small_only = false);      // 0: the kernel does not take these shapes

@@ -228,7 +228,7 @@ def device_status(reset=False):
 
 
 EPILOGUES = {None: 0, "log_softmax": 1, "relu_l2norm": 2}     # TTRNN_EPI_*
-ROUTES = {0: "valu", 1: "stagewise_mfma", 2: "fused_core", 3: "merged_big", 4: "runtime_mfma"}
+ROUTES = {0: "valu", 1: "stagewise_mfma", 2: "fused_core", 3: "merged_big", 4: "runtime_mfma", 5: "dense_step"}
 
 
 def make_ttm(in_modes, out_modes, ranks):
