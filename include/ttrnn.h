@@ -397,7 +397,9 @@ int ttrnn_rnn_varlen_seed_dout(const ttrnn_rnn_desc* desc, const int32_t* length
  *                      the workspace the forward left and may be called repeatedly; after a forward with need_grad == 0 the
  *                      results are NaN.  E and w are the forward's.
  * Every sum across workgroups goes through per-workgroup partials added in a fixed order: no atomics, results repeatable bit
- * for bit.  No allocation, no synchronisation, capture-safe; workspace of ttrnn_ge2e_workspace(desc) bytes (0 for a descriptor
+ * for bit; the sums over the utterances of a speaker are compensated or taken tile by tile, so the accuracy against float64
+ * (within 4 x the fp32 tensor-op formulation's own error, or 2^-19 of the largest magnitude) holds up to the row limit.  No
+ * allocation, no synchronisation, capture-safe; workspace of ttrnn_ge2e_workspace(desc) bytes (0 for a descriptor
  * the calls refuse).  TTRNN_ERR_BAD_DESC: non-positive sizes, U < 2 in the training form; TTRNN_ERR_UNSUPPORTED: S > 2048,
  * D > 4096 or more than 2^22 rows. */
 #define TTRNN_HAS_GE2E 1

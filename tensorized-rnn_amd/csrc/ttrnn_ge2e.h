@@ -15,7 +15,9 @@
 //   4  d_E         workgroup (s, utterance tile): slabs summed in a fixed order, the Jacobians of both normalisations, the
 //                  direct term; everything is linear in G = w dout, so w and the upstream gradient g multiply the result once
 // Phases 1-3 are the forward call, phase 4 the backward call: four launches for loss plus all gradients.  Every sum is taken
-// in an order fixed by the plan alone: no atomics, results repeatable bit for bit.  fp32 VALU arithmetic throughout.
+// in an order fixed by the plan alone: no atomics, results repeatable bit for bit.  fp32 VALU arithmetic throughout.  The sums
+// whose length is U or a chunk of rows keep their error independent of that length up to the row limit: the centroid sum of
+// phase 1 is compensated (over batches of sixteen), the sums of phase 3 are taken per tile of 256 rows from 0 and the tile totals added to the carry.
 // The operands are a few hundred KB and L2-resident: what the loops are shaped for is load latency — sixteen independent loads
 // are issued before the sixteen dependent FMAs that consume them, and values that every lane needs go through LDS.
 #pragma once
@@ -171,8 +173,24 @@ TT_HD void ge2e_centroid_body(Ex& ex, const Ge2ePlan& p, int j, const float* src
     float nn = 0.f;
     for (int d = tid; d < D; d += nthr) {
       const float* col = src + (size_t)j * Usrc * D + d;
-      float c = 0.f;
-      ge2e_batch16(0, Usrc, [&](int u) { return col[(size_t)u * D]; }, [&](int, float v) { c += v; });
+      // sixteen loads in flight, their sum as a tree of depth 4, and the batch totals in a compensated (Kahan) sum: `lost` carries
+      // what the running sum rounded away, so the error does not grow with Usrc and the dependent chain is 8 operations per batch
+      float c = 0.f, lost = 0.f;
+      for (int u0 = 0; u0 < Usrc; u0 += 16) {
+        float v[16];
+#pragma unroll
+        for (int m = 0; m < 16; ++m) v[m] = col[(size_t)(u0 + m < Usrc ? u0 + m : Usrc - 1) * D];
+#pragma unroll
+        for (int m = 0; m < 16; ++m) v[m] = u0 + m < Usrc ? v[m] : 0.f;
+#pragma unroll
+        for (int h = 8; h >= 1; h >>= 1)
+#pragma unroll
+          for (int m = 0; m < h; ++m) v[m] += v[m + h];
+        const float y = v[0] - lost;
+        const float t = c + y;
+        lost = (t - c) - y;
+        c = t;
+      }
       ws[p.o_csum + (size_t)j * D + d] = c;
       ws[p.o_csumT + (size_t)d * S + j] = c;
       const float m = c / (float)Usrc;
@@ -298,7 +316,9 @@ TT_HD void ge2e_rows_body(Ex& ex, const Ge2ePlan& p, int wg, const float* E, con
       for (int k = 0; k < C; ++k) a += part[(size_t)r * C + k];
       rsum[r] = a;
       const int s = (r0 + r) / U;
-      rloss[r] = (logf(a) + rmax[r]) - out[(size_t)r * S + s];
+      // log(sum) - (out_s - max): the difference is exact where the true class is the maximum (or near it), so a small loss
+      // keeps its own precision, not that of |out|
+      rloss[r] = logf(a) - (out[(size_t)r * S + s] - rmax[r]);
     }
   });
   ex.par([&](int tid, int nthr) {
@@ -373,21 +393,21 @@ TT_HD void ge2e_cgrad_body(Ex& ex, const Ge2ePlan& p, int kj, const float* E, fl
   for (int t0 = row0; t0 < row1; t0 += TTRNN_GE2E_TILE) {
     const int nt = row1 - t0 < TTRNN_GE2E_TILE ? row1 - t0 : TTRNN_GE2E_TILE;
     ex.par([&](int tid, int nthr) {
-      float t = t0 == row0 ? 0.f : red[tid];
+      float t = 0.f;
       for (int i = tid; i < nt; i += nthr) {
         const int row = t0 + i;
         const float g = (row < own0 || row >= own1) ? dout[(size_t)row * S + j] : 0.f;
         gl[i] = g;
         t += g * raw[(size_t)row * S + j];
       }
-      red[tid] = t;
+      red[tid] = t0 == row0 ? t : red[tid] + t;
     });
     ex.par([&](int tid, int nthr) {
       for (int d = tid; d < D; d += nthr) {
         const float* col = E + (size_t)t0 * D + d;
-        float a = t0 == row0 ? 0.f : slab[d];
+        float a = 0.f;
         ge2e_batch16(0, nt, [&](int i) { return col[(size_t)i * D]; }, [&](int i, float v) { a += gl[i] * v; });
-        slab[d] = a;
+        slab[d] = t0 == row0 ? a : slab[d] + a;
       }
     });
   }
@@ -426,12 +446,12 @@ TT_HD void ge2e_asum_body(Ex& ex, const Ge2ePlan& p, int s, const float* E, floa
       for (int d = tid; d < D; d += nthr) {
         const float c = ws[p.o_csum + (size_t)s * D + d];
         const float* col = E + ((size_t)s * U + u0) * D + d;
-        float a = u0 == 0 ? 0.f : asum[d];
+        float a = 0.f;
         ge2e_batch16(0, nt, [&](int i) { return col[(size_t)i * D]; }, [&](int i, float v) {
           const float* q = sc + 4 * i;
           a += ge2e_dv(c, v, um1, q[0], q[1], q[2], q[3]);
         });
-        asum[d] = a;
+        asum[d] = u0 == 0 ? a : asum[d] + a;
       }
     });
   }

@@ -26,9 +26,104 @@ EXTRA = [((3, 7, 30, 0), (3.7, 0.4, 3.5))]
 CASES = [(sh, sc) for sh in SHAPES for sc in SCALARS] + EXTRA
 
 
+# the loops that take more than one pass, the tile carries of phase 3 and the descriptors at the plan's limits
+LOOP_SHAPES = [
+    (3, 2, 300, 0),      # D just past one pass of the 256 threads: every `d = tid; d < D; d += nthr` loop runs twice for 44 threads
+    (2, 3, 4096, 0),     # D at the limit: sixteen passes, the largest LDS of the centroid phase
+    (300, 2, 5, 0),      # S > 256: R = P = 1 and npair = 300 > 256, the pair loops of the row phase take two passes
+    (2048, 2, 8, 0),     # S at the limit: 36 KB of LDS in the row phase, eight passes of its pair loops
+    (5, 3, 3, 0),        # D < P: DC = 1 and the split threads c >= D have an empty component range
+    (17, 257, 20, 0),    # N = 4369: CH = 274, two tiles in ge2e_cgrad_body; U = 257: two tiles in ge2e_asum_body
+    (3, 300, 12, 2),     # enrollment form with U > 256 verification rows per speaker, U_enroll = 2
+    (6, 2, 40, 300),     # enrollment form, the centroid sum runs over 300 enrollment rows
+]
+LOOP_CASES = [(sh, (10.0, -5.0, 3.5)) for sh in LOOP_SHAPES]
+# many rows per speaker: the sums over U (centroids, slabs, asum) must hold the accuracy rule up to the row limit
+LONG_SHAPES = [
+    (4, 20000, 8, 0),    # 79 tiles per chunk in ge2e_cgrad_body, 79 in ge2e_asum_body
+    (4, 3, 16, 100000),  # enrollment form: a centroid sum of 100000 rows
+    (2, 1 << 21, 4, 0),  # the row limit, 2^22 rows: 1024 tiles per chunk, 8192 per speaker
+]
+LONG_CASES = [(sh, (10.0, -5.0, 1.0)) for sh in LONG_SHAPES]
+
+
 def case_id(case):
     (S, U, D, Ue), (w, b, g) = case
     return "S%d-U%d-D%d-Ue%d-w%g-b%g-g%g" % (S, U, D, Ue, w, b, g)
+
+
+loop_id = long_id = case_id
+
+# (input builder, (w, b, g)): values of w, b and of the embeddings at which a softmax without max-subtraction overflows and at
+# which both arms of the two eps clamps are taken
+RANGE_CASES = [
+    ("unclustered", (300.0, -100.0, 1.0)),        # exp(out) overflows fp32 without the subtraction (|out| up to ~400)
+    ("unclustered", (-300.0, 50.0, 1.0)),         # negative w: the row maximum is the LEAST similar centroid
+    ("unclustered", (1000.0, 0.0, 1.0)),          # |out| up to ~1000
+    ("unclustered_enroll", (300.0, -100.0, 1.0)),  # the same through the enrollment form
+    ("zero_rows", (10.0, -5.0, 1.0)),             # exact zeros: an exclusive and an inclusive centroid of norm 0 (fl == 0 arms)
+    ("eps_straddle", (1e12, -5.0, 1.0)),          # centroid norms on both sides of eps = 1e-12
+]
+EPS = 1e-12
+
+
+def range_id(case):
+    name, (w, b, g) = case
+    return "%s-w%g-b%g-g%g" % (name, w, b, g)
+
+
+@functools.lru_cache(maxsize=None)
+def range_inputs(name):
+    """(E, A or None) of a RANGE_CASES builder, float32, CPU; shared, callers must not modify them."""
+    if name.startswith("unclustered"):
+        gen = torch.Generator().manual_seed(20240611)
+
+        def draw(n):
+            x = torch.randn(6, n, 24, generator=gen)
+            x = x / x.norm(dim=2, keepdim=True)
+            return (x * (0.5 + 1.5 * torch.rand(6, n, 1, generator=gen))).float().contiguous()
+
+        E = draw(3)
+        return E, (draw(2) if name == "unclustered_enroll" else None)
+    if name == "zero_rows":
+        E = inputs(4, 2, 16, 0)[0].clone()
+        E[1, 1] = 0      # the exclusive centroid of row (1, 0) is exactly 0, and row (1, 1) is a zero embedding
+        E[2] = 0         # a speaker whose inclusive centroid is exactly 0
+        return E, None
+    if name == "eps_straddle":
+        return (inputs(4, 3, 16, 0)[0] * 1e-12).contiguous(), None
+    raise KeyError(name)
+
+
+def centroid_norms(E):
+    """float64 norms of the inclusive centroids [S] and of the exclusive centroids [S, U] (training form)."""
+    e = E.double()
+    U = e.shape[1]
+    return e.mean(dim=1).norm(dim=1).numpy(), ((e.sum(dim=1, keepdim=True) - e) / (U - 1)).norm(dim=2).numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def range_reference(case):
+    """float64 on the CPU, once per range case; asserts first that the case exercises what it is there for."""
+    name, (w, b, g) = case
+    E, A = range_inputs(name)
+    ref = evaluate(E, A, w, b, g, torch.float64)
+    S, U, _ = E.shape
+    if name.startswith("unclustered"):
+        assert ref["loss"] > 1 and np.abs(ref["d_E"]).max() > 1e-3, (ref["loss"], np.abs(ref["d_E"]).max())
+        own = ref["sim"][np.arange(S), :, np.arange(S)]                  # [S, U]: every row's true-class entry
+        assert (own < ref["sim"].max(axis=2)).any()
+        assert np.abs(ref["sim"]).max() > 89                             # exp overflows fp32 above 88.7
+    elif name == "zero_rows":
+        incl, excl = centroid_norms(E)
+        assert incl[2] == 0 and excl[1, 0] == 0 and not E[1, 1].any() and not E[2].any()
+        assert (np.delete(incl, 2) > 0.1).all() and excl[0].min() > 0.1
+    elif name == "eps_straddle":
+        for n in centroid_norms(E):
+            assert (n < EPS).any() and (n > EPS).any(), n
+            assert np.abs(n / EPS - 1).min() > 1e-3, n
+        assert np.abs(ref["d_E"]).max() > 1e-3
+    return ref
 
 
 @functools.lru_cache(maxsize=None)

@@ -2,6 +2,7 @@
 // ttrnn_fast_ge2e.hip's four kernels, workgroup after workgroup and thread after thread, on the CPU.  Test infrastructure only
 // (tests/test_ge2e_fused_host.py builds it with g++); with -DHOSTEMU_GE2E_MAIN it is a stand-alone program over the same
 // bodies, which is the form a sanitizer build takes (g++ -fsanitize=address,undefined -DHOSTEMU_GE2E_MAIN ...).
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -11,11 +12,25 @@
 using namespace ttrnn;
 
 namespace {
+// the threads of one workgroup, one after the other in `order` (a permutation of 0 .. nthr - 1): a value that one thread writes
+// and another reads inside the same par comes out differently under another order, as it races on the device
 struct HostExec {
   int nthr;
+  const int* order;
   template <class F>
   void par(F f) {
-    for (int t = 0; t < nthr; ++t) f(t, nthr);
+    for (int i = 0; i < nthr; ++i) f(order[i], nthr);
+  }
+};
+
+// one workgroup's LDS: exactly the floats the device launch asks for, NaN before every workgroup body as nothing on the device
+// carries over from the workgroup before
+struct Lds {
+  std::vector<float> v;
+  explicit Lds(size_t n) : v(n) {}
+  float* fresh() {
+    std::fill(v.begin(), v.end(), NAN);
+    return v.data();
   }
 };
 }  // namespace
@@ -29,28 +44,37 @@ long hostemu_ge2e_workspace_floats(const ttrnn_ge2e_desc* desc) {
 }
 
 // forward (phases 1-3) + backward (phase 4) as the library's two calls make them; ws: hostemu_ge2e_workspace_floats floats,
-// filled with NaN here first so that a read of anything a phase did not write shows in the results
+// filled with NaN here first so that a read of anything a phase did not write shows in the results.  order: 0 = threads
+// 0 .. 255 in turn, 1 = 255 .. 0, any other value = the permutation that value seeds.
 int hostemu_ge2e(const ttrnn_ge2e_desc* desc, const float* E, const float* A, const float* w, const float* b, const float* g,
-                 float* loss, float* sim_out, int need_grad, float* dE, float* dw, float* db, float* ws) {
+                 float* loss, float* sim_out, int need_grad, float* dE, float* dw, float* db, float* ws, int order) {
   Ge2ePlan p;
   const int st = ge2e_plan_init(&p, desc);
   if (st != TTRNN_OK) return st;
   const int T = TTRNN_GE2E_THREADS;
-  HostExec ex{T};
+  int perm[TTRNN_GE2E_THREADS];
+  for (int t = 0; t < T; ++t) perm[t] = order == 1 ? T - 1 - t : t;
+  if (order != 0 && order != 1) {
+    unsigned seed = (unsigned)order;
+    for (int t = T - 1; t > 0; --t) {      // Fisher-Yates on a linear congruential generator
+      seed = seed * 1664525u + 1013904223u;
+      std::swap(perm[t], perm[(seed >> 8) % (unsigned)(t + 1)]);
+    }
+  }
+  HostExec ex{T, perm};
   for (size_t i = 0; i < p.total; ++i) ws[i] = NAN;
-  std::vector<float> lds(p.lds_rows + p.lds_cgrad + p.lds_dE + (size_t)p.D + TTRNN_GE2E_RED, NAN);
+  Lds l1((size_t)p.D + T + 17), l2(p.lds_rows), l3(p.lds_cgrad), l4(p.lds_dE);      // the four launches' dynamic LDS
   const bool train = p.Ue == 0;
-  for (int j = 0; j < p.S; ++j) ge2e_centroid_body(ex, p, j, train ? E : A, train ? p.U : p.Ue, ws, lds.data(), T);
-  for (int wg = 0; wg < p.nrow_wg; ++wg) ge2e_rows_body(ex, p, wg, E, w, b, sim_out, need_grad, ws, lds.data(), T);
-  ge2e_finalize_body(ex, p, loss, need_grad, ws, lds.data(), T);
-  if (need_grad && train)
-  {
-    for (int kj = 0; kj < p.K * p.S; ++kj) ge2e_cgrad_body(ex, p, kj, E, ws, lds.data(), T);
-    for (int s = 0; s < p.S; ++s) ge2e_asum_body(ex, p, s, E, ws, lds.data());
+  for (int j = 0; j < p.S; ++j) ge2e_centroid_body(ex, p, j, train ? E : A, train ? p.U : p.Ue, ws, l1.fresh(), T);
+  for (int wg = 0; wg < p.nrow_wg; ++wg) ge2e_rows_body(ex, p, wg, E, w, b, sim_out, need_grad, ws, l2.fresh(), T);
+  ge2e_finalize_body(ex, p, loss, need_grad, ws, l3.fresh(), T);
+  if (need_grad && train) {
+    for (int kj = 0; kj < p.K * p.S; ++kj) ge2e_cgrad_body(ex, p, kj, E, ws, l3.fresh(), T);
+    for (int s = 0; s < p.S; ++s) ge2e_asum_body(ex, p, s, E, ws, l3.fresh());
   }
   if (dE || dw || db) {
     const int grid = dE ? p.S * p.UTn : 1;
-    for (int wg = 0; wg < grid; ++wg) ge2e_dE_body(ex, p, wg, E, w, g, dE, dw, db, ws, lds.data());
+    for (int wg = 0; wg < grid; ++wg) ge2e_dE_body(ex, p, wg, E, w, g, dE, dw, db, ws, l4.fresh());
   }
   return TTRNN_OK;
 }
@@ -58,25 +82,35 @@ int hostemu_ge2e(const ttrnn_ge2e_desc* desc, const float* E, const float* A, co
 }  // extern "C"
 
 #ifdef HOSTEMU_GE2E_MAIN
-// every shape class the kernels distinguish (tails in D, one class, U = 2, a speaker past a 64 tile, the enrollment form) on
-// seeded inputs; prints the losses, exits non-zero on a non-finite result
+// every shape class the kernels distinguish (tails in D, one class, U = 2, a speaker past a 64 tile, the enrollment form; D past
+// one pass of the threads and at its limit, S past 256 and at its limit, D < P, two tiles in both tile loops of phase 3, long
+// sums in both forms) on seeded inputs, threads in forward, reverse and one shuffled order; prints the losses, exits non-zero on
+// a non-finite result or on a result that depends on the order
 int main() {
-  const int shapes[][4] = {{1, 2, 8, 0}, {5, 2, 32, 0}, {3, 7, 30, 0}, {65, 3, 256, 0}, {16, 32, 256, 0}, {7, 3, 36, 2}, {300, 2, 5, 0}};
+  const int shapes[][4] = {{1, 2, 8, 0},    {5, 2, 32, 0},   {3, 7, 30, 0},    {65, 3, 256, 0},  {16, 32, 256, 0}, {7, 3, 36, 2},
+                           {300, 2, 5, 0},  {3, 2, 300, 0},  {2, 3, 4096, 0},  {2048, 2, 2, 0},  {5, 3, 3, 0},     {17, 257, 4, 0},
+                           {3, 300, 4, 2},  {6, 2, 4, 300},  {2, 20000, 2, 0}, {2, 3, 2, 20000}};
   unsigned seed = 12345u;
   auto rnd = [&]() { seed = seed * 1664525u + 1013904223u; return (float)(seed >> 8) / 16777216.f - 0.5f; };
   for (const auto& sh : shapes) {
     ttrnn_ge2e_desc d{sh[0], sh[1], sh[2], sh[3]};
-    const size_t n = (size_t)d.S * d.U * d.D, na = (size_t)d.S * d.U_enroll * d.D;
-    std::vector<float> E(n), A(na), dE(n), sim((size_t)d.S * d.U * d.S), ws(hostemu_ge2e_workspace_floats(&d));
+    const size_t n = (size_t)d.S * d.U * d.D, na = (size_t)d.S * d.U_enroll * d.D, ns = (size_t)d.S * d.U * d.S;
+    std::vector<float> E(n), A(na), ws(hostemu_ge2e_workspace_floats(&d)), first;
     for (auto& v : E) v = rnd();
     for (auto& v : A) v = rnd();
-    float w = 10.f, b = -5.f, g = 3.5f, loss = 0.f, dw = 0.f, db = 0.f;
-    const int st = hostemu_ge2e(&d, E.data(), na ? A.data() : nullptr, &w, &b, &g, &loss, sim.data(), 1, dE.data(), &dw, &db, ws.data());
-    float amax = 0.f;      // a sum, so that one NaN shows
-    for (float v : dE) amax += fabsf(v);
-    std::printf("S %d U %d D %d Ue %d: status %d loss %.6f d_w %.3e d_b %.3e sum|d_E| %.3e\n", d.S, d.U, d.D, d.U_enroll, st, loss, dw,
-                db, amax);
-    if (st != TTRNN_OK || !(loss == loss) || !(amax == amax) || !(dw == dw)) return 1;
+    for (int order : {0, 1, 77}) {
+      std::vector<float> out(n + ns + 3, NAN);      // d_E, sim, loss, d_w, d_b
+      float w = 10.f, b = -5.f, g = 3.5f;
+      float *dE = out.data(), *sim = dE + n, *loss = sim + ns, *dw = loss + 1, *db = loss + 2;
+      const int st = hostemu_ge2e(&d, E.data(), na ? A.data() : nullptr, &w, &b, &g, loss, sim, 1, dE, dw, db, ws.data(), order);
+      float asum = 0.f;      // sums, so that one NaN shows
+      for (size_t i = 0; i < n + ns; ++i) asum += fabsf(out[i]);
+      std::printf("S %d U %d D %d Ue %d order %d: status %d loss %.6f d_w %.3e d_b %.3e sum|d_E|+|sim| %.3e\n", d.S, d.U, d.D,
+                  d.U_enroll, order, st, *loss, *dw, *db, asum);
+      if (st != TTRNN_OK || !(*loss == *loss) || !(asum == asum) || !(*dw == *dw) || !(*db == *db)) return 1;
+      if (first.empty()) first = out;
+      if (std::memcmp(first.data(), out.data(), out.size() * sizeof(float)) != 0) return 2;
+    }
   }
   return 0;
 }

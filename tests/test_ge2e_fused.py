@@ -53,6 +53,35 @@ def test_fused_matches_float64(case):
         assert got["loss"] == 0 and got["d_w"] == 0 and got["d_b"] == 0 and not got["d_E"].any()
 
 
+@pytest.mark.parametrize("case", C.LOOP_CASES, ids=C.loop_id)
+def test_fused_multi_pass_loops_match_float64(case):
+    """Strided loops of more than one pass, two tiles in both tile loops of phase 3, the descriptors at the plan's limits."""
+    (S, U, D, Ue), (w, b, g) = case
+    E, A = C.inputs(S, U, D, Ue)
+    got = to_np(run_fused(E, A, w, b, g))
+    C.check(got, C.reference(case), C.evaluate(E, A, w, b, g, torch.float32, dev()), C.loop_id(case))
+
+
+@pytest.mark.parametrize("case", C.RANGE_CASES, ids=C.range_id)
+def test_fused_value_ranges_match_float64(case):
+    """Large and negative w (the softmax's max-subtraction), exact zero centroids and centroid norms on both sides of eps."""
+    name, (w, b, g) = case
+    E, A = C.range_inputs(name)
+    ref = C.range_reference(case)
+    got = to_np(run_fused(E, A, w, b, g))
+    assert all(np.isfinite(v).all() for v in got.values())
+    C.check(got, ref, C.evaluate(E, A, w, b, g, torch.float32, dev()), C.range_id(case))
+
+
+@pytest.mark.parametrize("case", C.LONG_CASES, ids=C.long_id)
+def test_fused_long_sums_match_float64(case):
+    """Many rows per speaker, up to the row limit of 2^22: the sums over U of phases 1 and 3 under the same rule."""
+    (S, U, D, Ue), (w, b, g) = case
+    E, A = C.inputs(S, U, D, Ue)
+    got = to_np(run_fused(E, A, w, b, g))
+    C.check(got, C.reference(case), C.evaluate(E, A, w, b, g, torch.float32, dev()), C.long_id(case))
+
+
 @pytest.mark.parametrize("name", C.fixture_names())
 def test_fused_matches_reference_fixture(name):
     d, emb, enr = C.load_fixture(name)
@@ -62,7 +91,8 @@ def test_fused_matches_reference_fixture(name):
     assert float(np.abs(got["d_E"] - d["d_embeds"]).max()) <= 2e-6
 
 
-@pytest.mark.parametrize("shape", [(65, 3, 256, 0), (16, 32, 256, 0), (7, 3, 36, 2)], ids=str)
+@pytest.mark.parametrize("shape", [(65, 3, 256, 0), (16, 32, 256, 0), (7, 3, 36, 2), (17, 257, 20, 0), (300, 2, 5, 0), (3, 2, 300, 0)],
+                         ids=str)
 def test_bitwise_repeatable(shape):
     """Two calls; a workspace filled with NaN before the call (nothing is read that the call did not write); and the
     similarity matrix requested or not: identical bits every time."""
@@ -90,10 +120,68 @@ def test_bitwise_repeatable(shape):
     assert all(bool(torch.isnan(t).all()) for t in ge2e._fused_backward(state, g))
 
 
+def raw_call(E, A, w, b, g, with_loss=True, with_sim=True, want=(True, True, True)):
+    """ttrnn_ge2e_forward + ttrnn_ge2e_backward through ctypes with NULL for every output not asked for; every buffer (outputs
+    and workspace) holds NaN before the call, so an element the kernels do not write shows.  g: device scalar or None (NULL)."""
+    import ctypes
+    from ttrnn_hip import _lib, ge2e
+    desc, nbytes, E, A, wd, bd = ge2e._fused_operands(E, w, b, A)
+    S, U, _ = E.shape
+
+    def nan(*shape):
+        return torch.full(shape, float("nan"), dtype=torch.float32, device=dev())
+
+    ws = nan(nbytes // 4)
+    out = {"loss": nan() if with_loss else None, "sim": nan(S, U, S) if with_sim else None, "d_E": nan(*E.shape) if want[0] else None,
+           "d_w": nan() if want[1] else None, "d_b": nan() if want[2] else None}
+    lib, p = _lib.load(), ge2e._ptr
+    _lib.check(lib.ttrnn_ge2e_forward(ctypes.byref(desc), p(E), p(A), p(wd), p(bd), p(out["loss"]), p(out["sim"]), 1, p(ws), nbytes,
+                                      ge2e._stream(E)), "ttrnn_ge2e_forward")
+    _lib.check(lib.ttrnn_ge2e_backward(ctypes.byref(desc), p(E), p(wd), p(g), p(out["d_E"]), p(out["d_w"]), p(out["d_b"]), p(ws),
+                                       nbytes, ge2e._stream(E)), "ttrnn_ge2e_backward")
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("shape", [(7, 3, 36, 0), (7, 3, 36, 2)], ids=str)
+def test_nullable_outputs(shape):
+    """Every output the header allows to be NULL, left out: what is delivered has the bits of the call that asks for everything
+    (with d_E == NULL the backward is a one-workgroup grid), and no delivered element is left unwritten."""
+    E, A = C.inputs(*shape)
+    E, A = E.to(dev()), (A.to(dev()) if A is not None else None)
+    w, b = torch.tensor(10.0, device=dev()), torch.tensor(-5.0, device=dev())
+    g = torch.tensor(3.5, device=dev())
+    full = raw_call(E, A, w, b, g)
+    assert all(bool(torch.isfinite(t).all()) for t in full.values())
+    assert float(full["d_E"].abs().max()) > 0 and float(full["d_w"].abs()) > 0
+
+    def same(got, ref, keys):
+        assert {k for k, v in got.items() if v is not None} == set(keys)
+        for k in keys:
+            assert torch.equal(got[k], ref[k]), k      # NaN never compares equal: an unwritten element fails here too
+
+    same(raw_call(E, A, w, b, g, with_loss=False), full, ("sim", "d_E", "d_w", "d_b"))
+    same(raw_call(E, A, w, b, g, with_loss=False, with_sim=False), full, ("d_E", "d_w", "d_b"))
+    same(raw_call(E, A, w, b, g, want=(False, True, True)), full, ("loss", "sim", "d_w", "d_b"))
+    same(raw_call(E, A, w, b, g, want=(True, False, False)), full, ("loss", "sim", "d_E"))
+    same(raw_call(E, A, w, b, g, want=(False, False, True)), full, ("loss", "sim", "d_b"))
+    one = raw_call(E, A, w, b, torch.tensor(1.0, device=dev()))
+    same(raw_call(E, A, w, b, None), one, ("loss", "sim", "d_E", "d_w", "d_b"))
+    assert not torch.equal(one["d_E"], full["d_E"])
+
+
 def test_graph_capture_replays_on_new_values():
     """Loss + backward recorded on one stream; the replay reads the embeddings, w, b and the upstream gradient on the device."""
+    capture_and_replay(16, 32, 256)
+
+
+def test_graph_capture_replays_through_tile_carries():
+    """The same at two tiles per chunk in ge2e_cgrad_body and two per speaker in ge2e_asum_body."""
+    capture_and_replay(17, 257, 20)
+
+
+def capture_and_replay(S, U, D):
     from ttrnn_hip import ge2e
-    S, U, D = 16, 32, 256
     E0, _ = C.inputs(S, U, D, 0)
     e = E0.to(dev()).requires_grad_(True)
     w, b = scalars(10.0, -5.0)

@@ -35,7 +35,10 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else ctypes.c_void_p(0)
 
 
-def run_emu(emu, E, A, w, b, g):
+FORWARD, REVERSE = 0, 1      # hostemu_ge2e's thread orders; any other value seeds a permutation
+
+
+def run_emu(emu, E, A, w, b, g, order=FORWARD):
     """All four phases on numpy copies of the torch inputs -> dict as ge2e_fused_common.evaluate."""
     S, U, D = E.shape
     desc = _lib.Ge2eDesc(S, U, D, A.shape[1] if A is not None else 0)
@@ -47,7 +50,7 @@ def run_emu(emu, E, A, w, b, g):
     sim, d_E = np.full((S, U, S), np.nan, np.float32), np.full((S, U, D), np.nan, np.float32)
     sc = {k: np.full(1, v, np.float32) for k, v in (("w", w), ("b", b), ("g", g), ("loss", np.nan), ("dw", np.nan), ("db", np.nan))}
     st = emu.hostemu_ge2e(ctypes.byref(desc), _p(e), _p(a), _p(sc["w"]), _p(sc["b"]), _p(sc["g"]), _p(sc["loss"]), _p(sim), 1,
-                          _p(d_E), _p(sc["dw"]), _p(sc["db"]), _p(ws))
+                          _p(d_E), _p(sc["dw"]), _p(sc["db"]), _p(ws), ctypes.c_int(order))
     assert st == 0
     return {"sim": sim, "loss": sc["loss"][0], "d_E": d_E, "d_w": sc["dw"][0], "d_b": sc["db"][0]}
 
@@ -69,6 +72,47 @@ def test_host_bodies_match_float64(emu, case):
     C.check(got, C.reference(case), C.evaluate(E, A, w, b, g, torch.float32), C.case_id(case))
     if S == 1:
         assert got["loss"] == 0 and got["d_w"] == 0 and got["d_b"] == 0 and not got["d_E"].any()
+
+
+@pytest.mark.parametrize("case", C.LOOP_CASES, ids=C.loop_id)
+def test_host_bodies_multi_pass_loops_match_float64(emu, case):
+    """Strided loops of more than one pass, two tiles in both tile loops of phase 3, the descriptors at the plan's limits."""
+    (S, U, D, Ue), (w, b, g) = case
+    E, A = C.inputs(S, U, D, Ue)
+    C.check(run_emu(emu, E, A, w, b, g), C.reference(case), C.evaluate(E, A, w, b, g, torch.float32), C.loop_id(case))
+
+
+@pytest.mark.parametrize("case", C.LONG_CASES, ids=C.long_id)
+def test_host_bodies_long_sums_match_float64(emu, case):
+    """Many rows per speaker, up to the row limit: the sums over U of phases 1 and 3 under the same rule as every other shape."""
+    (S, U, D, Ue), (w, b, g) = case
+    E, A = C.inputs(S, U, D, Ue)
+    C.check(run_emu(emu, E, A, w, b, g), C.reference(case), C.evaluate(E, A, w, b, g, torch.float32), C.long_id(case))
+
+
+@pytest.mark.parametrize("case", C.RANGE_CASES, ids=C.range_id)
+def test_host_bodies_value_ranges_match_float64(emu, case):
+    """Large and negative w (the softmax's max-subtraction), exact zero centroids and centroid norms on both sides of eps."""
+    name, (w, b, g) = case
+    E, A = C.range_inputs(name)
+    ref = C.range_reference(case)
+    got = run_emu(emu, E, A, w, b, g)
+    assert all(np.isfinite(np.asarray(v)).all() for v in got.values())
+    C.check(got, ref, C.evaluate(E, A, w, b, g, torch.float32), C.range_id(case))
+
+
+@pytest.mark.parametrize("case", C.CASES + C.LOOP_CASES + C.RANGE_CASES, ids=lambda c: (C.range_id if isinstance(c[0], str) else C.case_id)(c))
+def test_thread_order_does_not_matter(emu, case):
+    """The threads of every par in forward, reverse and one shuffled order: identical bits.  A value written and read inside one
+    par without a barrier between would differ here, as it would race on the device."""
+    E, A = C.range_inputs(case[0]) if isinstance(case[0], str) else C.inputs(*case[0])
+    w, b, g = case[1]
+    first = run_emu(emu, E, A, w, b, g, FORWARD)
+    assert all(np.isfinite(np.asarray(v)).all() for v in first.values())
+    for order in (REVERSE, 4711):
+        other = run_emu(emu, E, A, w, b, g, order)
+        for key in ("sim", "loss", "d_E", "d_w", "d_b"):
+            assert np.array_equal(np.asarray(first[key]).view(np.uint32), np.asarray(other[key]).view(np.uint32)), (key, order)
 
 
 def test_entry_points_host_logic():
