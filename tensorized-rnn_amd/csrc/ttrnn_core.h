@@ -402,8 +402,9 @@ TT_HD void ttlinear_fwd_tile(Ex& ex, const TtShape& s, const float* W, const T* 
           for (int o = 1; o < out; ++o) m = row[o] > m ? row[o] : m;
           float sum = 0.f;
           for (int o = 0; o < out; ++o) sum += expf(row[o] - m);
-          a = m + logf(sum);
-          for (int o = 0; o < out; ++o) row[o] -= a;
+          const float ls = logf(sum);
+          a = m + ls;
+          for (int o = 0; o < out; ++o) row[o] = (row[o] - m) - ls;      // (not row[o] - a: k_head_epilogue in ttrnn_head.hip says why)
         } else {
           float sum = 0.f;
           for (int o = 0; o < out; ++o) { const float u = row[o] > 0.f ? row[o] : 0.f; sum += u * u; }

@@ -48,8 +48,9 @@ int hostemu_unpack(const ttrnn_ttm* w, const float* packed_grad, float* const* g
   return 0;
 }
 
+// epi / aux: the row-wise epilogue inside the tile (TTRNN_EPI_*, 0 = none) and where it leaves the log-sum-exp / L2 norm (may be NULL)
 int hostemu_ttlinear_forward(const ttrnn_ttm* w, int64_t n_rows, const float* packed, const float* bias,
-                             const float* x, float* y, int nb, int nthr) {
+                             const float* x, float* y, int nb, int nthr, int epi, float* aux) {
   TtShape s;
   int st = tt_shape_init(&s, w);
   if (st != TTRNN_OK) return st;
@@ -58,7 +59,7 @@ int hostemu_ttlinear_forward(const ttrnn_ttm* w, int64_t n_rows, const float* pa
   HostExec ex{nthr};
   for (int64_t n0 = 0; n0 < n_rows; n0 += nb) {
     const int n = (int)tmin<int64_t>(nb, n_rows - n0);
-    ttlinear_fwd_tile<HostExec, float>(ex, s, packed, bias, x, y, n0, n, A.data(), B.data(), bs);
+    ttlinear_fwd_tile<HostExec, float>(ex, s, packed, bias, x, y, n0, n, A.data(), B.data(), bs, 0, 0, epi, aux);
   }
   return 0;
 }

@@ -114,7 +114,7 @@ def test_hostemu_ttlinear(emu, name):
     x = case.arr["x"]
     y = np.zeros((x.shape[0], tt.out_f), dtype=np.float32)
     assert emu.hostemu_ttlinear_forward(ctypes.byref(tt.desc), ctypes.c_int64(x.shape[0]), _p(tt.packed), _p(tt.bias),
-                                        _p(x), _p(y), 2, 37) == 0
+                                        _p(x), _p(y), 2, 37, 0, _p(None)) == 0
     assert _maxabs(y, case.arr["y"]) <= 2e-6
     dx, dcores, db = tt.backward(x, case.arr["w"])
     scale = lambda e: 1e-5 * max(float(np.abs(e).max()), 1e-6) + 1e-7
@@ -208,3 +208,118 @@ def test_hostemu_rnn(emu, name):
         assert _maxabs(d_h0_tot, case.arr["grad_h0"]) <= scale(case.arr["grad_h0"])
     if "grad_c0" in case.arr:
         assert _maxabs(d_c0_tot, case.arr["grad_c0"]) <= scale(case.arr["grad_c0"])
+
+
+# ---- the row-wise epilogue inside ttlinear_fwd_tile (the one-launch narrow heads of csrc/ttrnn_head.hip, out <= 32) -----------------
+# Against a float64 evaluation (the oracle's chain + the formula of include/ttrnn.h), per tensor:
+#     err <= max(4 x the error of a float32 evaluation of the same formula, 2^-19 x max|reference|)
+HEAD_OUT_MODES = {2: [1, 1, 2], 10: [1, 2, 5], 32: [2, 4, 4]}
+
+
+def _head_tt(emu, width, bias, seed):
+    rng = np.random.RandomState(seed)
+    jm, im, ranks = [4, 8, 8], HEAD_OUT_MODES[width], [1, 8, 8, 1]
+    cores = [(rng.standard_normal((ranks[k], im[k], jm[k], ranks[k + 1])) * (jm[k] * ranks[k + 1]) ** -0.5).astype(np.float32)
+             for k in range(3)]
+    return Tt(emu, cores, [tuple(s // 4 for s in c.strides) for c in cores], bias), cores
+
+
+def _head_eval(cores, bias, x, epi, dtype):
+    """(y, aux) in `dtype` arithmetic: the oracle's chain, then log_softmax (epi 1) or ReLU + division by the 2-norm (epi 2)."""
+    import torch
+    from oracle import ttrnn_oracle as O
+    tt = torch.float64 if dtype == np.float64 else torch.float32
+    z = O.ttlinear([torch.from_numpy(c).to(tt) for c in cores], None if bias is None else torch.from_numpy(bias).to(tt),
+                   torch.from_numpy(x).to(tt)).numpy()
+    assert z.dtype == dtype
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if epi == 1:
+            m = z.max(axis=1, keepdims=True)
+            aux = m[:, 0] + np.log(np.exp(z - m).sum(axis=1))
+            return z, z - aux[:, None], aux
+        u = np.maximum(z, 0)
+        aux = np.sqrt((u * u).sum(axis=1))
+        return z, u / aux[:, None], aux
+
+
+def _head_emu(emu, tt, x, epi, nb, nthr, want_aux=True):
+    y = np.full((x.shape[0], tt.out_f), np.nan, dtype=np.float32)
+    aux = np.full(x.shape[0], np.nan, dtype=np.float32) if want_aux else None
+    assert emu.hostemu_ttlinear_forward(ctypes.byref(tt.desc), ctypes.c_int64(x.shape[0]), _p(tt.packed), _p(tt.bias), _p(x),
+                                        _p(y), nb, nthr, epi, _p(aux)) == 0
+    return y, aux
+
+
+def _head_check(emu, tt, cores, x, epi):
+    """Every (nb, nthr) gives the same bits; the values meet the bound.  A ReLU row without a positive entry is 0 / 0 = NaN in
+    the emulated kernel exactly where it is in the float32 and the float64 evaluation; the bound covers the other rows."""
+    z64, y64, a64 = _head_eval(cores, tt.bias, x, epi, np.float64)
+    _, y32, a32 = _head_eval(cores, tt.bias, x, epi, np.float32)
+    runs = [_head_emu(emu, tt, x, epi, nb, nthr) for nb in (1, 2, 5) for nthr in (1, 37, 64)]
+    y, aux = runs[0]
+    for yy, aa in runs[1:]:
+        assert np.array_equal(y, yy, equal_nan=True) and np.array_equal(aux, aa, equal_nan=True)
+    assert np.array_equal(_head_emu(emu, tt, x, epi, 2, 37, want_aux=False)[0], y, equal_nan=True)      # aux == NULL
+    assert np.array_equal(np.isnan(y), np.isnan(y32)) and np.array_equal(np.isnan(y), np.isnan(y64))
+    keep = [r for r in range(x.shape[0]) if not np.isnan(y64[r]).any()]
+    assert keep
+    for name, got, f32, ref in (("y", y, y32, y64), ("aux", aux, a32, a64)):
+        got, f32, ref = got[keep], f32[keep], ref[keep]
+        err, err32 = _maxabs(got, ref), _maxabs(f32, ref)
+        bound = max(4.0 * err32, 2.0 ** -19 * float(np.abs(ref).max()))
+        print("%-4s max|ref| %.3e  emulated kernel %.3e  float32 %.3e  bound %.3e" % (name, np.abs(ref).max(), err, err32, bound))
+        assert err <= bound, (name, err, err32, bound)
+    return z64, y, aux
+
+
+@pytest.mark.parametrize("bias", [True, False], ids=["bias", "nobias"])
+@pytest.mark.parametrize("epi", [1, 2], ids=["log_softmax", "relu_l2norm"])
+@pytest.mark.parametrize("width", sorted(HEAD_OUT_MODES))
+def test_hostemu_head_epilogue(emu, width, epi, bias):
+    rng = np.random.RandomState(100 + width)
+    b = (rng.standard_normal(width) * 0.1).astype(np.float32) if bias else None
+    tt, cores = _head_tt(emu, width, b, width)
+    for n in (1, 3, 4, 5, 37):
+        _head_check(emu, tt, cores, rng.standard_normal((n, 256)).astype(np.float32), epi)
+
+
+def _edge_x(rng, n=6, scale=0.5):
+    x = (rng.standard_normal((n, 256)) * scale).astype(np.float32)
+    x[0] = 0.0                      # row 0: the pre-activation is the bias itself
+    return x
+
+
+@pytest.mark.parametrize("width", sorted(HEAD_OUT_MODES))
+def test_hostemu_head_epilogue_edge_rows(emu, width):
+    rng = np.random.RandomState(200 + width)
+    # logits spread over +-80 around +300: exp() of them overflows fp32 without the max-subtraction
+    b = (300.0 + 80.0 * np.linspace(-1, 1, width)[rng.permutation(width)]).astype(np.float32)
+    tt, cores = _head_tt(emu, width, b, width)
+    z, y, aux = _head_check(emu, tt, cores, _edge_x(rng), 1)
+    assert z[0].max() - z[0].min() == 160.0 and z[0].min() == 220.0 and np.isfinite(y).all() and np.isfinite(aux).all()
+    # the maximum occurs twice
+    b = rng.standard_normal(width).astype(np.float32)
+    b[0] = b[width - 1] = b.max() + 1.0
+    tt, cores = _head_tt(emu, width, b, width + 1)
+    z, y, aux = _head_check(emu, tt, cores, _edge_x(rng), 1)
+    assert (z[0] == z[0].max()).sum() == 2
+    # exactly one positive entry: the unit vector
+    b = (-rng.random_sample(width) - 0.1).astype(np.float32)
+    b[1] = 0.7
+    tt, cores = _head_tt(emu, width, b, width + 2)
+    z, y, aux = _head_check(emu, tt, cores, _edge_x(rng), 2)
+    assert (z[0] > 0).sum() == 1 and y[0, 1] == 1.0 and (y[0] != 0).sum() == 1 and aux[0] == b[1]
+    # no positive entry: 0 / 0 = NaN, as float32 norm + divide; the other rows are unaffected
+    b = (-rng.random_sample(width) - 0.1).astype(np.float32)
+    tt, cores = _head_tt(emu, width, b, width + 3)
+    z, y, aux = _head_check(emu, tt, cores, _edge_x(rng, scale=4.0), 2)
+    assert (z[0] > 0).sum() == 0 and np.isnan(y[0]).all() and aux[0] == 0.0
+    assert sum(1 for r in range(1, 6) if (z[r] > 0).any() and np.isfinite(y[r]).all()) >= 2
+    # norms of 1e-15 and 1e15
+    for s in (1e-15, 1e15):
+        b = ((0.5 + 0.5 * rng.random_sample(width)) * s).astype(np.float32)
+        b[::2] = -b[::2]
+        tt, cores = _head_tt(emu, width, b, width + 4)
+        z, y, aux = _head_check(emu, tt, cores, _edge_x(rng), 2)
+        n0 = np.sqrt((np.maximum(z[0], 0) ** 2).sum())
+        assert 0.1 * s <= n0 <= 100.0 * s and np.isfinite(y[0]).all() and np.isfinite(aux).all()
