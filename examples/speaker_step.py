@@ -31,6 +31,9 @@ def main():
     ap.add_argument("-n", "--nruns", type=int, default=10)
     ap.add_argument("--torch_loss", action="store_true",
                     help="GE2E loss as torch tensor ops + autograd instead of the library's GE2E kernels (A/B)")
+    ap.add_argument("--eer", action="store_true",
+                    help="also time the step with the EER computed every step on the device (with_eer=\"device\": no host "
+                         "round trip; the value is read once, after the loop), as the reference's step reports loss and EER")
     args = ap.parse_args()
     dev = torch.device("cuda")
     torch.manual_seed(11)
@@ -41,29 +44,39 @@ def main():
     S, U = args.speakers, args.utterances
     x = torch.rand(S * U, args.frames, args.mels, device=dev)
 
-    def step():
+    def step(with_eer=False):
         opt.zero_grad(set_to_none=True)
         embeds = model(x).view(S, U, -1)
-        loss, _ = model.loss(embeds, fused=False if args.torch_loss else None, with_eer=False)
+        loss, eer = model.loss(embeds, fused=False if args.torch_loss else None, with_eer=with_eer)
         loss.backward()
         model.do_gradient_ops()
         opt.step()
-        return loss
+        return loss, eer
 
-    loss = step()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(args.nruns):
-        t0 = time.perf_counter()
-        loss = step()
+    def timed(with_eer):
+        out = step(with_eer)
         torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
+        times = []
+        for _ in range(args.nruns):
+            t0 = time.perf_counter()
+            out = step(with_eer)
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        return times, out
+
+    times, (loss, _) = timed(False)
+    if args.eer:
+        times_eer, (loss_eer, eer_dev) = timed("device")
     with torch.no_grad():
         embeds = model(x).view(S, U, -1)
         _, eer = model.loss(embeds)
     ms = 1e3 * sum(times) / len(times)
     print("speaker-encoder train step (%s GE2E loss): %.2f ms (min %.2f) for %d utterances x %d frames; loss %.4f, EER %.3f" % (
         "torch-op" if args.torch_loss else "fused", ms, 1e3 * min(times), S * U, args.frames, float(loss), eer))
+    if args.eer:
+        ms_eer = 1e3 * sum(times_eer) / len(times_eer)
+        print("... with the EER on the device every step: %.2f ms (min %.2f), %+.3f ms against the step without it; "
+              "loss %.4f, EER of the last step %.3f" % (ms_eer, 1e3 * min(times_eer), ms_eer - ms, float(loss_eer), float(eer_dev)))
     if args.dense:
         from ttrnn_hip import functional as TF
         spec = model.rnn.cell0._layer_spec()

@@ -390,7 +390,7 @@ int ttrnn_rnn_varlen_seed_dout(const ttrnn_rnn_desc* desc, const int32_t* length
  *   sim[s,u,j] = E[s,u] . incl_j (j != s),  sim[s,u,s] = E[s,u] . excl_su                      (speaker_encoder.py:109-124)
  * Enrollment form: sim[s,u,j] = E[s,u] . normalize(mean_u A[j,u])                                (speaker_encoder.py:125-130)
  * Both: out = w sim + b;  loss = mean over the S U rows of cross_entropy(out[row,:], s), softmax max-subtracted (:154-159).
- * ttrnn_ge2e_forward   writes loss (NULL-able) and, when sim_out != NULL, out[S][U][S] (what the host-side EER reads, :161-169).
+ * ttrnn_ge2e_forward   writes loss (NULL-able) and, when sim_out != NULL, out[S][U][S] (what the EER reads, :161-169: ttrnn_ge2e_eer).
  *                      need_grad != 0 leaves in the workspace what ttrnn_ge2e_backward reads; three launches (centroids, rows,
  *                      centroid gradients + the loss's final sum).
  * ttrnn_ge2e_backward  one launch: d_E[S][U][D], d_w, d_b (each NULL-able) for the upstream gradient *g (NULL = 1).  It reads
@@ -414,6 +414,41 @@ int ttrnn_ge2e_forward(const ttrnn_ge2e_desc* desc, const float* E, const float*
                        float* sim_out, int need_grad, void* workspace, size_t workspace_bytes, void* stream);
 int ttrnn_ge2e_backward(const ttrnn_ge2e_desc* desc, const float* E, const float* w, const float* g, float* d_E, float* d_w,
                         float* d_b, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- equal error rate of the GE2E similarity matrix (additive to ABI 7: test for TTRNN_HAS_GE2E_EER) -----------------------------
+ * The second number of the reference's speaker-verification step (speaker_encoder.py:160-168: roc_curve + interp1d + brentq on
+ * the host), computed on the device from the sim_out of ttrnn_ge2e_forward (either form) with no host round trip.
+ *   sim   fp32 [S][U][S], contiguous, read only; element [s][u][j] is a positive iff j == s: P = S U positives,
+ *         Nn = S U (S - 1) negatives.
+ * With (fp, tp) the negatives / positives at or above a score: theta is the LARGEST score with fp P + tp Nn >= Nn P, (fp', tp')
+ * are the counts strictly above theta, and
+ *   a = Nn P - (fp' P + tp' Nn),  b = (fp - fp') P + (tp - tp') Nn,  eer = (fp' + (a / b) (fp - fp')) / Nn
+ * evaluated in IEEE double from exact 64-bit integers: the point where the ROC polyline, vertical segments included, meets
+ * tpr = 1 - fpr (what roc_curve / interp1d / brentq return to within brentq's xtol).  Scores are compared by value through an
+ * order-preserving 32-bit key of their bits: -0 and +0 are one value (theta is then +0), subnormals are distinct values, +-inf
+ * are ordinary extremes.  theta is found by a four-pass radix selection with two integer histograms per digit; nothing is sorted
+ * and no temporary has the size of the matrix.
+ *   eer        DEVICE double;  threshold (NULL-able) DEVICE float = theta;  counts (NULL-able) DEVICE int64 [4] = tp', fp', tp, fp.
+ *   any NaN score:  eer = NaN, threshold = NaN, every count = -1.
+ *   desc.route       0 = the library's choice (one workgroup up to 24576 scores, a grid above), 1 = one workgroup, one launch,
+ *                    2 = a grid of workgroups, five launches
+ *   desc.workgroups  route 2 only: 0 = the library's choice (sqrt(S U S) / 12, within 1 .. 256), else exactly this many, 1 .. 256;
+ *                    each takes a contiguous chunk of ceil(S U S / workgroups) scores (the last ones may be short or empty)
+ * Integer counts only: the outputs are identical bits for every route, workgroup count and execution order.  No allocation, no
+ * synchronisation, no host read, capture-safe; cross-workgroup totals go through per-workgroup partial histograms written with
+ * plain stores and read behind a kernel boundary (no global atomics).  workspace: ttrnn_ge2e_eer_workspace(desc) bytes (0 for a
+ * descriptor the call refuses), contents on entry irrelevant.  Decided before any launch — TTRNN_ERR_BAD_DESC: S < 2, U < 1,
+ * route outside 0 .. 2, workgroups negative, above 256 or non-zero with route != 2; TTRNN_ERR_UNSUPPORTED: S > 2048,
+ * S U > 2^22 or S U S > 2^30; TTRNN_ERR_NULL: desc, sim, eer or workspace NULL; TTRNN_ERR_WORKSPACE. */
+#define TTRNN_HAS_GE2E_EER 1
+typedef struct ttrnn_eer_desc {
+  int32_t S, U;          /* sim is fp32 [S][U][S]                                              */
+  int32_t route;         /* 0 = library's choice, 1 = one workgroup / one launch, 2 = grid     */
+  int32_t workgroups;    /* route 2 only: 0 = library's choice, else exactly this many (1..256) */
+} ttrnn_eer_desc;
+size_t ttrnn_ge2e_eer_workspace(const ttrnn_eer_desc* desc);
+int ttrnn_ge2e_eer(const ttrnn_eer_desc* desc, const float* sim, double* eer, float* threshold, int64_t* counts, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* Reverse-time part of BPTT (reference: torch autograd through lstm.py:123-133 / gru.py:124-134).
  *   d_out[B][T][H], d_hT/d_cT[B][H] (any may be NULL = zeros)

@@ -57,6 +57,11 @@ class Ge2eDesc(ctypes.Structure):
     _fields_ = [("S", ctypes.c_int32), ("U", ctypes.c_int32), ("D", ctypes.c_int32), ("U_enroll", ctypes.c_int32)]
 
 
+class EerDesc(ctypes.Structure):
+    """struct ttrnn_eer_desc (include/ttrnn.h, TTRNN_HAS_GE2E_EER)"""
+    _fields_ = [("S", ctypes.c_int32), ("U", ctypes.c_int32), ("route", ctypes.c_int32), ("workgroups", ctypes.c_int32)]
+
+
 _P = ctypes.c_void_p
 _SIGNATURES = {
     "ttrnn_abi_version": (ctypes.c_int, []),
@@ -112,6 +117,9 @@ _SIGNATURES = {
     "ttrnn_ge2e_workspace": (ctypes.c_size_t, [ctypes.POINTER(Ge2eDesc)]),
     "ttrnn_ge2e_forward": (ctypes.c_int, [ctypes.POINTER(Ge2eDesc), _P, _P, _P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_size_t, _P]),
     "ttrnn_ge2e_backward": (ctypes.c_int, [ctypes.POINTER(Ge2eDesc), _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    # equal error rate of the similarity matrix (TTRNN_HAS_GE2E_EER): desc, sim, eer, threshold, counts, workspace, bytes, stream
+    "ttrnn_ge2e_eer_workspace": (ctypes.c_size_t, [ctypes.POINTER(EerDesc)]),
+    "ttrnn_ge2e_eer": (ctypes.c_int, [ctypes.POINTER(EerDesc), _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "ttrnn_rnn_backward_workspace": (ctypes.c_size_t, [ctypes.POINTER(RnnDesc)]),
     "ttrnn_rnn_backward_workspace_ex": (ctypes.c_size_t, [ctypes.POINTER(RnnDesc), ctypes.c_int]),
     "ttrnn_rnn_backward_route": (ctypes.c_int, [ctypes.POINTER(RnnDesc), ctypes.c_int]),

@@ -45,13 +45,25 @@ def eer(sim2d, S, U):
 
 
 def ge2e_loss(verification, weight, bias, enrollment=None, with_eer=True):
-    """(softmax loss over all S*U utterances, EER or None) — speaker_encoder.py:142-170."""
+    """(softmax loss over all S*U utterances, EER or None) — speaker_encoder.py:142-170.  with_eer="device": the EER as a 0-d
+    float64 device tensor from eer_fused (fp32 GPU similarities only; TtrnnError otherwise), with no synchronisation."""
     S, U, _ = verification.shape
     sim = similarity_matrix(verification, weight, bias, enrollment).reshape(S * U, S)
     target = torch.arange(S, device=sim.device).repeat_interleave(U)
     loss = F.cross_entropy(sim, target)
+    if _on_device(with_eer):
+        return loss, eer_fused(sim.detach(), S, U)
     e = eer(sim.detach().float().cpu().numpy(), S, U) if with_eer else None
     return loss, e
+
+
+def _on_device(with_eer):
+    """with_eer is True / False / None (the host-side EER, or none) or the string "device"."""
+    if isinstance(with_eer, str):
+        if with_eer != "device":
+            raise ValueError('with_eer must be True, False, None or "device", got {!r}'.format(with_eer))
+        return True
+    return False
 
 
 class _GatherSpeakers(torch.autograd.Function):
@@ -202,10 +214,71 @@ def ge2e_loss_fused(verification, weight, bias, enrollment=None, with_eer=False)
     if enrollment is not None and enrollment.requires_grad:
         raise _lib.TtrnnError("the fused GE2E loss has no gradient to the enrollment embeddings (detach them)")
     S, U, _ = verification.shape
+    device_eer = _on_device(with_eer)
     if not with_eer:
         return _FusedGE2E.apply(verification, weight, bias, enrollment, False), None
     loss, sim = _FusedGE2E.apply(verification, weight, bias, enrollment, True)
+    if device_eer:      # two more launches at most, on the same stream; nothing is read on the host
+        return loss, eer_fused(sim, S, U)
     return loss, eer(sim.reshape(S * U, S).cpu().numpy(), S, U)
+
+
+# ---- the equal error rate of the similarity matrix as a library call (include/ttrnn.h, TTRNN_HAS_GE2E_EER) -----------------------
+
+EER_ROUTES = {"auto": 0, "one": 1, "grid": 2}      # ttrnn_eer_desc.route
+EER_MAX_WORKGROUPS = 256
+
+
+@functools.lru_cache(maxsize=64)
+def _eer_plan(S, U, route, workgroups):
+    """(descriptor, workspace bytes; 0 = refused) — pure host arithmetic in the library, cached per shape and route."""
+    desc = _lib.EerDesc(S, U, route, workgroups)
+    return desc, int(_lib.load().ttrnn_ge2e_eer_workspace(ctypes.byref(desc)))
+
+
+def eer_supported(S, U, dtype, device):
+    """True when eer_fused takes a [S, U, S] similarity matrix of this dtype on this device: fp32 on a GPU, 2 <= S <= 2048,
+    S U <= 2^22, S U S <= 2^30."""
+    if dtype != torch.float32 or torch.device(device).type != "cuda":
+        return False
+    S, U = int(S), int(U)
+    if not (0 <= S < 2 ** 31 and 0 <= U < 2 ** 31):
+        return False
+    return _eer_plan(S, U, 0, 0)[1] > 0
+
+
+def eer_fused(sim, S=None, U=None, want_aux=False, route="auto", workgroups=0):
+    """Equal error rate of a similarity matrix, [S, U, S] or [S U, S] fp32 on a GPU, as one library call: what `eer` returns
+    (to within brentq's tolerance) as a 0-d float64 tensor on sim's device, with no synchronisation and nothing read on the host,
+    so it can be captured.  want_aux: (eer, threshold 0-d float32, counts int64 [4] = tp', fp', tp, fp around the threshold).
+    route: "auto", "one" (one workgroup, one launch) or "grid" (`workgroups` workgroups, 0 = the library's choice; five launches);
+    every route returns the same bits.  A NaN score gives eer = threshold = NaN and counts of -1 (the host route raises there).
+    Raises TtrnnError on CPU tensors, other dtypes and shapes the kernels refuse — there is no fallback to the host route."""
+    if not torch.is_tensor(sim) or not sim.is_cuda or sim.dtype != torch.float32:
+        raise _lib.TtrnnError("eer_fused runs on float32 GPU tensors only (got {} on {}); there is no fallback — call eer for the "
+                              "host route".format(getattr(sim, "dtype", type(sim)), getattr(sim, "device", "the host")))
+    if sim.dim() == 3 and sim.shape[0] == sim.shape[2]:
+        s_, u_ = sim.shape[0], sim.shape[1]
+    elif sim.dim() == 2 and sim.shape[1] > 0 and sim.shape[0] % sim.shape[1] == 0:
+        s_, u_ = sim.shape[1], sim.shape[0] // sim.shape[1]
+    else:
+        raise _lib.TtrnnError("the similarity matrix must be [S, U, S] or [S U, S], got {}".format(tuple(sim.shape)))
+    if (S is not None and int(S) != s_) or (U is not None and int(U) != u_):
+        raise _lib.TtrnnError("a similarity matrix of shape {} is not S={} U={}".format(tuple(sim.shape), S, U))
+    if route not in EER_ROUTES and route not in EER_ROUTES.values():
+        raise ValueError("route must be one of {}".format(sorted(EER_ROUTES)))
+    desc, nbytes = _eer_plan(s_, u_, EER_ROUTES.get(route, route), int(workgroups))
+    if nbytes == 0:
+        raise _lib.TtrnnError("the EER kernels do not take S={} U={} route={} workgroups={}".format(s_, u_, route, workgroups))
+    x = sim.detach().contiguous()
+    with _on(x.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        out = torch.empty((), dtype=torch.float64, device=x.device)
+        thr = torch.empty((), dtype=torch.float32, device=x.device) if want_aux else None
+        cnt = torch.empty(4, dtype=torch.int64, device=x.device) if want_aux else None
+        _lib.check(_lib.load().ttrnn_ge2e_eer(ctypes.byref(desc), _ptr(x), _ptr(out), _ptr(thr), _ptr(cnt), _ptr(ws), ws.numel(),
+                                              _stream(x)), "ttrnn_ge2e_eer")
+    return (out, thr, cnt) if want_aux else out
 
 
 def ge2e_loss_data_parallel(local_embeds, weight, bias, group=None, with_eer=False, force_gather=False, fused=False):
@@ -214,7 +287,8 @@ def ge2e_loss_data_parallel(local_embeds, weight, bias, group=None, with_eer=Fal
     unscaled) and back-propagates into its slice.  After the gradient all-reduce (MEAN) of the data-parallel step
     (ttrnn_hip.dist.FlatGradAllReduce) every parameter holds its single-device gradient: the slice gradient is scaled by
     the world size in _GatherSpeakers.backward, the replicated similarity weight / bias are left alone.
-    (The reference computes the loss on one CPU, main.py:280.)  fused=True: the full loss after the gather is ge2e_loss_fused."""
+    (The reference computes the loss on one CPU, main.py:280.)  fused=True: the full loss after the gather is ge2e_loss_fused.
+    with_eer="device": the EER of the full matrix as a device scalar (eer_fused), the same on every rank."""
     import os
     import torch.distributed as dist
     loss_fn = ge2e_loss_fused if fused else ge2e_loss

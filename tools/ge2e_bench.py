@@ -4,7 +4,12 @@
   ge2e_bench.py loss [--calls 200 --blocks 5]   loss forward + backward alone at (16,32,256), (64,10,256) and the (40,32,256)
                                                 enrollment forward: both paths alternate in blocks inside one process; per
                                                 block the device-event time and the host wall time (final synchronise) per call
-  ge2e_bench.py steps [-n 20]                   examples/speaker_step.py at its defaults and at the H = 768 first-tier shape,
+  ge2e_bench.py eer [--calls 200 --blocks 5]    equal error rate per eager call: ge2e.eer_fused (library's choice, one workgroup,
+                                                a grid with the workgroup count swept) against the host route (sim.cpu() +
+                                                ge2e.eer) at (16,32), (64,10), (40,32) with ttrnn_ge2e_forward with / without
+                                                sim_out alongside, then route 1 against route 2 from 65 K to 8.4 M scores; exit
+                                                status 1 unless route 0 beats the host route at the three reference shapes
+  ge2e_bench.py steps [-n 20]                  examples/speaker_step.py at its defaults and at the H = 768 first-tier shape,
                                                 each with and without --torch_loss, one child process per run under its own
                                                 time limit; stops at the first run that fails
   ge2e_bench.py count TRACE.csv                 launches of a kernel trace (rocprofv3 --kernel-trace --stats --output-format
@@ -78,6 +83,90 @@ def cmd_loss(args):
     return 0
 
 
+def _blocks(fns, calls, blocks, sync):
+    """The callables of `fns` (name -> f) alternate in blocks of `calls` calls; per block the host wall time per call around a
+    final synchronise, and the device-event span per call.  -> {name: (median wall us, spread, median device us, spread)}"""
+    import torch
+    for f in fns.values():
+        for _ in range(3):
+            f()
+    sync()
+    res = {name: ([], []) for name in fns}
+    for _ in range(blocks):
+        for name, f in fns.items():
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            sync()
+            t0 = time.perf_counter()
+            start.record()
+            for _ in range(calls):
+                f()
+            stop.record()
+            sync()
+            res[name][0].append(1e6 * (time.perf_counter() - t0) / calls)
+            res[name][1].append(1e3 * start.elapsed_time(stop) / calls)
+    return {name: (statistics.median(w), max(w) - min(w), statistics.median(g), max(g) - min(g)) for name, (w, g) in res.items()}
+
+
+def _show(label, r):
+    for name, (wall, wspread, gpu, gspread) in r.items():
+        print("%-22s %-24s host wall %9.1f us/call (spread %.1f)   device span %9.1f us/call (spread %.1f)" % (
+            label, name, wall, wspread, gpu, gspread), flush=True)
+
+
+def cmd_eer(args):
+    """Equal error rate: the device routes (ge2e.eer_fused) against the host route (sim.cpu() + ge2e.eer), per eager call."""
+    import torch
+    from ttrnn_hip import ge2e
+    dev = torch.device("cuda", 0)
+    sync = torch.cuda.synchronize
+    print("device:", torch.cuda.get_device_name(0), "| calls per block", args.calls, "| blocks", args.blocks)
+    print("every time is per eager call: host wall = perf_counter around a block ending in a synchronise; device span = events around it")
+    verdicts = []
+    print("\n-- the reference's shapes: library's choice, both routes, the host route (its result is a host float: it synchronises) --")
+    for S, U, Ue in ((16, 32, 0), (64, 10, 0), (40, 32, 32)):
+        E, A = _inputs(S, U, 256, Ue, dev)
+        w, b = torch.tensor([10.0], device=dev), torch.tensor([-5.0], device=dev)
+        sim = ge2e.similarity_matrix_fused(E, w, b, A)
+        host = ge2e.eer(sim.reshape(S * U, S).cpu().numpy(), S, U)
+        got = float(ge2e.eer_fused(sim))
+        fns = {"device route=0": lambda: ge2e.eer_fused(sim), "device route=1": lambda: ge2e.eer_fused(sim, route="one")}
+        for g in (1, 2, 4, 8, 16, 64):
+            fns["device route=2 wg=%d" % g] = (lambda g=g: ge2e.eer_fused(sim, route="grid", workgroups=g))
+        fns["host sim.cpu()+eer"] = lambda: ge2e.eer(sim.reshape(S * U, S).cpu().numpy(), S, U)
+        r = _blocks(fns, args.calls, args.blocks, sync)
+        label = "(%d,%d)%s %d scores" % (S, U, " U_e=%d" % Ue if Ue else "", S * U * S)
+        _show(label, r)
+        ok = r["device route=0"][0] < r["host sim.cpu()+eer"][0]
+        verdicts.append(ok)
+        print("%-22s EER device %.12f host %.12f (difference %.2e);  route=0 faster than the host route: %s (%.1fx)" % (
+            label, got, host, abs(got - host), "PASS" if ok else "FAIL", r["host sim.cpu()+eer"][0] / r["device route=0"][0]))
+        fwd = {"ge2e forward, no sim_out": lambda: ge2e._fused_forward(E, w, b, A, want_sim=False),
+               "ge2e forward + sim_out": lambda: ge2e._fused_forward(E, w, b, A, want_sim=True),
+               "... + sim_out + EER": lambda: ge2e.eer_fused(ge2e._fused_forward(E, w, b, A, want_sim=True)[1])}
+        _show(label, _blocks(fwd, args.calls, args.blocks, sync))
+    print("\n-- where the routes cross: route 1 against route 2 by score count (random scores; the host route once per shape) --")
+    gen = torch.Generator().manual_seed(5)
+    for S, U in ((128, 4), (128, 16), (256, 8), (256, 16), (512, 8), (1024, 4), (2048, 2)):
+        sim = torch.randn(S, U, S, generator=gen).to(dev)
+        fns = {"device route=1": lambda: ge2e.eer_fused(sim, route="one")}
+        for g in (4, 16, 64, 128, 256):
+            fns["device route=2 wg=%d" % g] = (lambda g=g: ge2e.eer_fused(sim, route="grid", workgroups=g))
+        fns["device route=2 wg=0"] = lambda: ge2e.eer_fused(sim, route="grid")
+        fns["device route=0"] = lambda: ge2e.eer_fused(sim)
+        label = "(%d,%d) %d scores" % (S, U, S * U * S)
+        r = _blocks(fns, max(args.calls // 4, 5), args.blocks, sync)
+        _show(label, r)
+        best = min((v[0], k) for k, v in r.items() if "route=2" in k)
+        print("%-22s route 1 %.1f us, best grid %s %.1f us" % (label, r["device route=1"][0], best[1], best[0]), flush=True)
+        if S * U * S <= 1 << 21:
+            t0 = time.perf_counter()
+            host = ge2e.eer(sim.reshape(S * U, S).cpu().numpy(), S, U)
+            print("%-22s host route, one call: %.1f ms; EER host %.12f device %.12f" % (
+                label, 1e3 * (time.perf_counter() - t0), host, float(ge2e.eer_fused(sim))), flush=True)
+    print("\nroute=0 faster than the host route at the three reference shapes:", "PASS" if all(verdicts) else "FAIL")
+    return 0 if all(verdicts) else 1
+
+
 def cmd_steps(args):
     step = os.path.join(ROOT, "examples", "speaker_step.py")
     shapes = ([], ["--hidden_size", "768", "--n_layers", "1", "--ncores", "2", "--ttrank", "2"])
@@ -131,13 +220,16 @@ def main():
     p = sub.add_parser("loss")
     p.add_argument("--calls", type=int, default=200)
     p.add_argument("--blocks", type=int, default=5)
+    p = sub.add_parser("eer")
+    p.add_argument("--calls", type=int, default=200)
+    p.add_argument("--blocks", type=int, default=5)
     p = sub.add_parser("steps")
     p.add_argument("-n", type=int, default=20)
     p.add_argument("--limit", type=int, default=240, help="seconds per child process")
     p = sub.add_parser("count")
     p.add_argument("trace")
     args = ap.parse_args()
-    return {"loss": cmd_loss, "steps": cmd_steps, "count": cmd_count}[args.cmd](args)
+    return {"loss": cmd_loss, "eer": cmd_eer, "steps": cmd_steps, "count": cmd_count}[args.cmd](args)
 
 
 if __name__ == "__main__":
