@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--graph", action="store_true",
                     help="--train only: record the step once into a hipGraph (ttrnn_hip.CapturedTrainStep) and time replays")
+    ap.add_argument("--fused_optim", action="store_true",
+                    help="--train only: the Adam step as one library call (ttrnn_hip.ClipAdam) instead of torch.optim.Adam")
     args = ap.parse_args()
     device = torch.device("cuda")
     with contextlib.redirect_stdout(io.StringIO()):
@@ -43,10 +45,14 @@ def main():
     data = torch.from_numpy(np.random.rand(args.batch_size, args.seq_len, args.in_size).astype("float32")).to(device)
     target = torch.from_numpy(np.random.randint(0, args.emb_size, args.batch_size).astype("int64")).to(device)
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+    if args.fused_optim and args.train:
+        import ttrnn_hip
+        opt = ttrnn_hip.ClipAdam(model.parameters(), lr=1e-3)
     captured = None
     if args.graph and args.train:
         import ttrnn_hip
-        opt = ttrnn_hip.adam_for_capture(model.parameters(), lr=1e-3)
+        if not args.fused_optim:
+            opt = ttrnn_hip.adam_for_capture(model.parameters(), lr=1e-3)
         captured = ttrnn_hip.CapturedTrainStep(model, opt, lambda m, d, t: F.nll_loss(m(d), t), (data, target))
 
     def step():

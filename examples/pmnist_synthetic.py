@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-2)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--seed", type=int, default=1111)
+    ap.add_argument("--fused_optim", action="store_true",
+                    help="--clip and the Adam step as one library call (ttrnn_hip.ClipAdam) instead of clip_grad_norm_ + torch.optim.Adam")
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     device = torch.device("cuda")
@@ -39,7 +41,11 @@ def main():
                                 n_cores=args.ncores, tt_rank=args.ttrank, naive_tt=args.naive_tt,
                                 extra_core=args.extra_core).to(device)
     permute = torch.randperm(seq_length) if args.permute else torch.arange(seq_length)
-    opt = torch.optim.Adam(model.parameters(), lr=args.lr)
+    if args.fused_optim:
+        import ttrnn_hip
+        opt = ttrnn_hip.ClipAdam(model.parameters(), lr=args.lr, max_norm=args.clip if args.clip > 0 else None)
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     sched = torch.optim.lr_scheduler.StepLR(opt, step_size=10, gamma=0.5)
     # a fixed synthetic "dataset": class-dependent means so that the loss can actually go down
     protos = torch.rand(n_classes, 28 * 28)
@@ -50,7 +56,7 @@ def main():
         opt.zero_grad()
         loss = F.nll_loss(model(data), target.to(device))
         loss.backward()
-        if args.clip > 0:
+        if args.clip > 0 and not args.fused_optim:
             torch.nn.utils.clip_grad_norm_(model.parameters(), args.clip)
         opt.step()
         sched.step()

@@ -34,13 +34,21 @@ def main():
     ap.add_argument("--eer", action="store_true",
                     help="also time the step with the EER computed every step on the device (with_eer=\"device\": no host "
                          "round trip; the value is read once, after the loop), as the reference's step reports loss and EER")
+    ap.add_argument("--fused_optim", action="store_true",
+                    help="gradient scaling, norm clipping and the Adam step as one library call (ttrnn_hip.ClipAdam) instead of "
+                         "do_gradient_ops() + torch.optim.Adam (A/B)")
     args = ap.parse_args()
     dev = torch.device("cuda")
     torch.manual_seed(11)
     with contextlib.redirect_stdout(io.StringIO()):
         model = SpeakerEncoder(args.mels, args.hidden_size, args.n_layers, args.emb_size, dev, n_cores=args.ncores,
                                rank=args.ttrank, use_gru=args.gru, compression=None if args.dense else 'tt').to(dev)
-    opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+    if args.fused_optim:
+        import ttrnn_hip
+        opt = ttrnn_hip.ClipAdam(model.parameters(), lr=1e-3, max_norm=3.0,
+                                 grad_scales={model.similarity_weight: 0.01, model.similarity_bias: 0.01})
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     S, U = args.speakers, args.utterances
     x = torch.rand(S * U, args.frames, args.mels, device=dev)
 
@@ -49,7 +57,8 @@ def main():
         embeds = model(x).view(S, U, -1)
         loss, eer = model.loss(embeds, fused=False if args.torch_loss else None, with_eer=with_eer)
         loss.backward()
-        model.do_gradient_ops()
+        if not args.fused_optim:
+            model.do_gradient_ops()
         opt.step()
         return loss, eer
 
@@ -71,8 +80,9 @@ def main():
         embeds = model(x).view(S, U, -1)
         _, eer = model.loss(embeds)
     ms = 1e3 * sum(times) / len(times)
-    print("speaker-encoder train step (%s GE2E loss): %.2f ms (min %.2f) for %d utterances x %d frames; loss %.4f, EER %.3f" % (
-        "torch-op" if args.torch_loss else "fused", ms, 1e3 * min(times), S * U, args.frames, float(loss), eer))
+    print("speaker-encoder train step (%s GE2E loss%s): %.2f ms (min %.2f) for %d utterances x %d frames; loss %.4f, EER %.3f" % (
+        "torch-op" if args.torch_loss else "fused", ", fused optimizer" if args.fused_optim else "", ms, 1e3 * min(times), S * U,
+        args.frames, float(loss), eer))
     if args.eer:
         ms_eer = 1e3 * sum(times_eer) / len(times_eer)
         print("... with the EER on the device every step: %.2f ms (min %.2f), %+.3f ms against the step without it; "

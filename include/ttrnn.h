@@ -450,6 +450,71 @@ size_t ttrnn_ge2e_eer_workspace(const ttrnn_eer_desc* desc);
 int ttrnn_ge2e_eer(const ttrnn_eer_desc* desc, const float* sim, double* eer, float* threshold, int64_t* counts, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ---- gradient scaling, global-norm clipping and the Adam step as one call (additive to ABI 7: test for TTRNN_HAS_OPTIM) ----------
+ * The tail of the reference's training steps after loss.backward(): speaker_encoder.py:61-67 (do_gradient_ops: the similarity
+ * parameters' gradients x 0.01, clip_grad_norm_(3.0)) + main.py:77-78 (do_gradient_ops, optimizer.step(); :252 Adam);
+ * pmnist_test.py:139,160-163 (Adam, optional --clip, StepLR) and benchmarking.py:43,56 (Adam) — in torch a foreach norm, a stack,
+ * a second norm, a clamp, a foreach multiply and the optimizer's own launches.  fp32 only.
+ *   numel       HOST int64 [n_tensors]
+ *   params, grads   HOST arrays [n_tensors] of DEVICE pointers: tensor i is numel[i] consecutive fp32 words at each (any dense
+ *               layout; both are walked in memory order, so a gradient must have its parameter's strides).  Any alignment:
+ *               128-bit accesses where a tensor's pointers are 16-byte aligned, 32-bit ones otherwise.
+ *   grad_scale  HOST float [n_tensors], NULL = ones
+ *   m, v        DEVICE fp32, ttrnn_optim_state_elems() words each: the moments.  The table is cut into CHUNKS of
+ *               TTRNN_OPTIM_CHUNK elements that never span two tensors; tensor i owns ceil(numel[i] / CHUNK) chunks and its
+ *               segment of m / v starts at word CHUNK x (chunks of the tensors before it): position k of the segment belongs to
+ *               word k of the tensor.  The padding words are never read or written.
+ *   step        DEVICE int64: the number of steps taken so far; the call writes step + 1
+ *   lr          DEVICE float: read at run time, so a captured graph replays with a new learning rate (StepLR) and a running counter
+ *   total_norm  DEVICE float, NULL-able: the norm BEFORE clipping
+ * Semantics (torch.nn.utils.clip_grad_norm_ + torch.optim.Adam), per element of tensor i, in fp32 with every operation rounded on
+ * its own:
+ *   g = grad_scale[i] grad;  total_norm = |all g|_2;  coef = min(max_norm / (total_norm + 1e-6), 1), exactly 1 when max_norm <= 0
+ *   (the multiply happens even when coef is 1; a NaN norm gives a NaN coef);  g <- coef g, stored to grads[i] when write_grads != 0;
+ *   g' = g + weight_decay p;  m <- beta1 m + (1 - beta1) g';  v <- beta2 v + ((1 - beta2) g') g';  t = *step + 1;
+ *   p <- p - (lr / (1 - beta1^t)) (m / (sqrt(v) / sqrt(1 - beta2^t) + eps));  *step <- t.
+ * The bias corrections are evaluated in double on the device from the integer counter.  Non-finite values propagate as the
+ * formulas say, as in torch; there is no error_if_nonfinite (it would synchronise).
+ *   mode TTRNN_OPTIM_CLIP_ONLY: g <- coef grad_scale[i] grad is stored and nothing else is touched: params, m, v, step and lr are
+ *   ignored (may be NULL), and so is write_grads; the descriptor's Adam fields are still checked.
+ * total_norm is the square root of a sum of per-chunk fp32 partials, each folded in an order fixed by the element index, added in
+ * chunk order in double: p, m, v, g and total_norm are IDENTICAL BITS for every route, workgroup count and execution order and
+ * whatever the workspace held on entry.  No global atomics; no workgroup waits on another; the counter is written once.
+ *   desc.route       0 = the library's choice (one workgroup up to 24 chunks of the table, a grid above),
+ *                    1 = one workgroup (one launch for a table of at most TTRNN_OPTIM_GROUP tensors), 2 = a grid
+ *   desc.workgroups  route 2 only: 0 = the library's choice (a workgroup per 4 chunks of the argument group, at most 1024), else
+ *                    exactly this many per launch, 1 .. 4096
+ * The pointer tables travel to the kernels by value in the kernel arguments, TTRNN_OPTIM_GROUP tensors per launch (gradients
+ * are fresh allocations every eager step; a captured step bakes in the pointers of its static gradients): route 2 is two
+ * launches per group of tensors, all first launches before the first second one, so the norm spans every group; without
+ * clipping and without total_norm the first launches shrink to one workgroup that advances the counter.
+ * No allocation, no synchronisation, no host <-> device copy, capture-safe; launches go to `stream`.  workspace:
+ * ttrnn_optim_workspace() bytes (0 for a descriptor the call refuses), contents on entry irrelevant.  Decided before any launch
+ * — TTRNN_ERR_BAD_DESC: n_tensors < 1, a numel < 1, mode outside 0 .. 1, route outside 0 .. 2, workgroups negative, above 4096
+ * or non-zero with route != 2, a beta outside [0, 1), eps not a finite value > 0, weight_decay not a finite value >= 0, max_norm
+ * NaN; TTRNN_ERR_UNSUPPORTED: n_tensors > 4096, 2^31 elements or more in all; TTRNN_ERR_NULL: desc, numel, grads, workspace or a
+ * gradient pointer NULL, and in mode TTRNN_OPTIM_ADAM params, a parameter pointer, m, v, step or lr; TTRNN_ERR_WORKSPACE. */
+#define TTRNN_HAS_OPTIM 1
+#define TTRNN_OPTIM_CHUNK 1024         /* elements per partial: part of the numerical contract          */
+#define TTRNN_OPTIM_GROUP 128          /* tensors per argument group (= per launch)                     */
+#define TTRNN_OPTIM_ADAM 0
+#define TTRNN_OPTIM_CLIP_ONLY 1        /* scale + clip the gradients in place, touch nothing else       */
+typedef struct ttrnn_optim_desc {
+  int32_t n_tensors;
+  int32_t mode;          /* TTRNN_OPTIM_ADAM / TTRNN_OPTIM_CLIP_ONLY                                    */
+  int32_t route;         /* 0 = library's choice, 1 = one workgroup, 2 = grid                           */
+  int32_t workgroups;    /* route 2 only: 0 = library's choice, else exactly this many (1..4096)        */
+  int32_t write_grads;   /* != 0: the scaled and clipped gradients are stored to grads[i]               */
+  float beta1, beta2, eps;
+  float weight_decay;    /* L2: added to the gradient after clipping, as torch.optim.Adam               */
+  float max_norm;        /* <= 0: no clipping                                                           */
+} ttrnn_optim_desc;
+int64_t ttrnn_optim_state_elems(const ttrnn_optim_desc* desc, const int64_t* numel);   /* floats in each of m and v; 0 = refused */
+size_t ttrnn_optim_workspace(const ttrnn_optim_desc* desc, const int64_t* numel);
+int ttrnn_optim_step(const ttrnn_optim_desc* desc, const int64_t* numel, void* const* params, void* const* grads,
+                     const float* grad_scale, float* m, float* v, int64_t* step, const float* lr, float* total_norm,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* Reverse-time part of BPTT (reference: torch autograd through lstm.py:123-133 / gru.py:124-134).
  *   d_out[B][T][H], d_hT/d_cT[B][H] (any may be NULL = zeros)
  *   -> d_gates_in[B][T][G*H], d_gates_hid[B][T][G*H] (fp32: gradients w.r.t. the outputs of the

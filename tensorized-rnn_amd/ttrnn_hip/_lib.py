@@ -62,6 +62,16 @@ class EerDesc(ctypes.Structure):
     _fields_ = [("S", ctypes.c_int32), ("U", ctypes.c_int32), ("route", ctypes.c_int32), ("workgroups", ctypes.c_int32)]
 
 
+class OptimDesc(ctypes.Structure):
+    """struct ttrnn_optim_desc (include/ttrnn.h, TTRNN_HAS_OPTIM)"""
+    _fields_ = [("n_tensors", ctypes.c_int32), ("mode", ctypes.c_int32), ("route", ctypes.c_int32), ("workgroups", ctypes.c_int32),
+                ("write_grads", ctypes.c_int32), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("max_norm", ctypes.c_float)]
+
+
+OPTIM_CHUNK, OPTIM_GROUP = 1024, 128          # TTRNN_OPTIM_CHUNK, TTRNN_OPTIM_GROUP
+OPTIM_ADAM, OPTIM_CLIP_ONLY = 0, 1
+
 _P = ctypes.c_void_p
 _SIGNATURES = {
     "ttrnn_abi_version": (ctypes.c_int, []),
@@ -120,6 +130,13 @@ _SIGNATURES = {
     # equal error rate of the similarity matrix (TTRNN_HAS_GE2E_EER): desc, sim, eer, threshold, counts, workspace, bytes, stream
     "ttrnn_ge2e_eer_workspace": (ctypes.c_size_t, [ctypes.POINTER(EerDesc)]),
     "ttrnn_ge2e_eer": (ctypes.c_int, [ctypes.POINTER(EerDesc), _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    # gradient scaling / norm clipping / Adam step (TTRNN_HAS_OPTIM): desc, numel, params, grads, grad_scale, m, v, step, lr,
+    # total_norm, workspace, bytes, stream
+    "ttrnn_optim_state_elems": (ctypes.c_int64, [ctypes.POINTER(OptimDesc), ctypes.POINTER(ctypes.c_int64)]),
+    "ttrnn_optim_workspace": (ctypes.c_size_t, [ctypes.POINTER(OptimDesc), ctypes.POINTER(ctypes.c_int64)]),
+    "ttrnn_optim_step": (ctypes.c_int, [ctypes.POINTER(OptimDesc), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_P),
+                                        ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_float), _P, _P, _P, _P, _P, _P, ctypes.c_size_t,
+                                        _P]),
     "ttrnn_rnn_backward_workspace": (ctypes.c_size_t, [ctypes.POINTER(RnnDesc)]),
     "ttrnn_rnn_backward_workspace_ex": (ctypes.c_size_t, [ctypes.POINTER(RnnDesc), ctypes.c_int]),
     "ttrnn_rnn_backward_route": (ctypes.c_int, [ctypes.POINTER(RnnDesc), ctypes.c_int]),
